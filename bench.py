@@ -97,7 +97,33 @@ def parse():
     ap.add_argument("--plumbing-only", action="store_true",
                     help="run only the multi-rank plumbing (launch, rendezvous, weight-style broadcast, barriers, "
                          "max-over-ranks) and print the JSON skeleton: works without a GPU (gloo)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step decoded as DIR/<name>.npy (float32, at most "
+                         "64 MB over all ranks; a seeded sample of the clips when the whole output is larger)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, frames, rank, world):
+    """What the timed path returned in its last step, as float32 .npy files under ``out_dir``.  ``frames`` is one rank's
+    (clips, 30, 3, H, W) decode; every rank writes its own file (``frames.npy`` for one rank, ``frames_rank<r>.npy``
+    otherwise) within an equal share of DUMP_LIMIT_BYTES.  Beyond that share a fixed, seeded choice of whole frames is
+    written as (k, 3, H, W), in order, with their flat indices clip * 30 + frame in ``<name>_index.npy``."""
+    os.makedirs(out_dir, exist_ok=True)
+    name = "frames" if world == 1 else f"frames_rank{rank}"
+    flat = frames.reshape(-1, *frames.shape[2:])
+    per_frame = flat[0].numel() * 4
+    keep = max(1, (DUMP_LIMIT_BYTES // world - 4096) // (per_frame + 8))
+    if keep < flat.shape[0]:
+        idx = np.sort(np.random.default_rng(4321 + rank).choice(flat.shape[0], keep, replace=False))
+        frames = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, f"{name}.npy"), frames.float().cpu().numpy())
 
 
 def source_sha():
@@ -505,6 +531,8 @@ def main():
     for v in D.gather_over_ranks(L.range_events(), device):
         events |= int(v)
     assert frames.shape == (n_own, 30, 3, 128, 128) and bool(torch.isfinite(frames).all())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, frames, rank, world)
     seen = int(D.sum_over_ranks(1, device))
 
     # how much of a step is ELIC key-frame decoding (latency-bound: 10 host round trips per batch)

@@ -162,3 +162,36 @@ def test_bench_parent_launches_before_any_gpu_call(monkeypatch):
     except SystemExit as e:
         assert e.code == 0
     assert calls and calls[0][2] == 4 and calls[0][1] == ["--gpus", "4", "--steps", "1"]
+
+
+def test_bench_dump_outputs_float32_within_64_mb(tmp_path):
+    """``bench.py --dump-outputs DIR``: the last step's frames as float32 .npy, all of them when they fit (configs[1]: 9 clips,
+    one rank), otherwise a seeded, sorted choice of whole frames with their flat indices -- the same choice on every run --
+    and never more than 64 MB over all ranks."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_under_test3", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    frames = torch.rand(9, 30, 3, 128, 128, generator=torch.Generator().manual_seed(0))
+    bench.dump_outputs(str(tmp_path / "one"), frames, 0, 1)
+    assert sorted(os.listdir(tmp_path / "one")) == ["frames.npy"]
+    got = np.load(tmp_path / "one" / "frames.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frames.numpy())
+    for run in ("a", "b"):
+        for rank in range(2):
+            bench.dump_outputs(str(tmp_path / run), frames, rank, 2)
+    assert sorted(os.listdir(tmp_path / "a")) == ["frames_rank0.npy", "frames_rank0_index.npy", "frames_rank1.npy",
+                                                  "frames_rank1_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    idx = np.load(tmp_path / "a" / "frames_rank0_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    sample = np.load(tmp_path / "a" / "frames_rank0.npy")
+    assert sample.dtype == np.float32 and np.array_equal(sample, frames.reshape(-1, 3, 128, 128).numpy()[idx.astype(int)])
+
+
+def test_bench_rejects_zero_timed_steps():
+    rc, line, err = _run_bench(["--steps", "0", "--plumbing-only"], {"EVC_DIST_BACKEND": "gloo"})
+    assert rc == 2 and line is None and "--steps" in err
