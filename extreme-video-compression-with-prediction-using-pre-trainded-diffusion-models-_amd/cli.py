@@ -20,6 +20,8 @@ import time
 import numpy as np
 import torch
 
+from .recovery import NumericsError  # noqa: F401  (raised by check_numerics and by the decoder's range recovery)
+
 DEFAULT_PATHS = [f"checkpoints/neural network/{i}.pth.tar" for i in range(6)]
 
 
@@ -74,6 +76,10 @@ def build_parser():
     p.add_argument("--bitstream-dir", type=str, default=None,
                    help="mask policy: write each batch's key-frame strings + mask as an EVC1 container here and "
                         "decode from the bytes read back (container.py)")
+    p.add_argument("--range-recovery", choices=["off", "layer"], default=None,
+                   help="layer: when a chunk raises an fp16-split range event, demote only the layers that raised it to the "
+                        "bf16x6 split and regenerate the chunk with the same noise (default: EVC_RANGE_RECOVERY, else off: "
+                        "the run stops with the remedy)")
     return p
 
 
@@ -111,11 +117,7 @@ def resolve_policy(args, log=print):
     return args.policy
 
 
-class NumericsError(RuntimeError):
-    pass
-
-
-def check_numerics(frames, where):
+def check_numerics(frames, where, note=""):
     """The fp16-split arithmetic clamps nothing (include/evc_hip.h EVC_RANGE_*): an operand beyond fp16's range becomes NaN
     and the sticky range-event word says so.  Never write such frames: stop with the remedy."""
     from . import lib as L
@@ -125,7 +127,17 @@ def check_numerics(frames, where):
         raise NumericsError(
             f"{where}: range-event word {ev:#x}, frames finite: {finite}.  A GroupNorm-ed or moment-bounded operand of the "
             f"score network left fp16's range (or a tensor held NaN / inf) under the default f16x3 arithmetic; rerun with "
-            f"EVC_CONV_ARITH=bf16x6 (exact 3-way bf16 split, no range assumption; about half the throughput) or =f32")
+            f"EVC_CONV_ARITH=bf16x6 (exact 3-way bf16 split, no range assumption; about half the throughput) or =f32"
+            + (f", or with --range-recovery layer (only the layers that raise the event move to bf16x6)" if not note else "")
+            + note)
+
+
+def recovery_note(dec):
+    """check_numerics' remark when recovery was asked for but the network has no event sites to demote."""
+    if dec.range_recovery == "layer" and not dec.recovers():
+        return (f".  Range recovery (--range-recovery layer) is built for the unetmore score networks only, not for "
+                f"{type(dec.net).__name__}: this network keeps stopping here")
+    return ""
 
 
 def cal_psnr(a, b, maxvalue=1.0):
@@ -236,7 +248,8 @@ def main(argv=None):
         mask = all_generated_mask()
         for q in args.q:
             model = models[q]
-            dec = ClipDecoder(net, model, cfg, S.get_sampler(args.sampler), groups=args.groups)
+            dec = ClipDecoder(net, model, cfg, S.get_sampler(args.sampler), groups=args.groups,
+                              range_recovery=args.range_recovery, log=lambda m: print(f"[rank {rank}] {m}", flush=True))
             for b0 in range(0, len(vids), max(1, args.batch)):
                 chunk = vids[b0:b0 + max(1, args.batch)]
                 gt = torch.from_numpy(np.stack([np.asarray(data[v], dtype=np.float32) / 255.0 for v in chunk]))
@@ -256,7 +269,7 @@ def main(argv=None):
                     with open(path, "rb") as fh:          # refuses a stream coded under another arithmetic
                         d_rx, keys_rx, shape_rx = container.unpack(fh.read(), expect_codec=model.codec_tag())
                 frames = dec.decode(d_rx, keys_rx, shape_rx, generator=gen)[..., :gt.shape[-2], :gt.shape[-1]]
-                check_numerics(frames, f"videos {chunk[0]}..{chunk[-1]} q{q}")
+                check_numerics(frames, f"videos {chunk[0]}..{chunk[-1]} q{q}", recovery_note(dec))
                 x_all = frames.cpu().numpy()
                 for j, vid in enumerate(chunk):
                     bits = [count_bits([[[[p[j]] for p in sl] for sl in k[0]], [k[1][j]]]) for k in keys]
@@ -266,7 +279,8 @@ def main(argv=None):
         # `--policy-batch` jobs per score-network launch; key frames coded once per (video, q, frame).
         from . import policy as P
         metric = P.load_metric(args.policy, args.metric, device)
-        dec = ClipDecoder(net, None, cfg, S.get_sampler(args.sampler))
+        dec = ClipDecoder(net, None, cfg, S.get_sampler(args.sampler), range_recovery=args.range_recovery,
+                          log=lambda m: print(f"[rank {rank}] {m}", flush=True))
         clips = {vid: torch.from_numpy(np.asarray(data[vid], dtype=np.float32) / 255.0) for vid in vids}
         res = P.run_policy(dec, models, clips, args.q, thresholds, metric, patch=args.patch, max_batch=args.policy_batch,
                            seed=args.seed, device=device, bpp_limit=args.bpp_limit, log=lambda m: print(f"[rank {rank}] {m}", flush=True))
@@ -274,7 +288,7 @@ def main(argv=None):
         for vid in vids:
             for q in args.q:
                 for r in res[(vid, q)]:
-                    check_numerics(r["x"], f"video {vid} q{q} thr {r['thr']:.2f}")
+                    check_numerics(r["x"], f"video {vid} q{q} thr {r['thr']:.2f}", recovery_note(dec))
                     report(vid, q, r["thr"], r["x"], clips[vid].numpy(), r["bits"], r["d"], store)
                     if args.policy == "lpips":      # per-frame distances of the decoded clip (city_sender.py:570-571)
                         v = metric.values(torch.from_numpy(r["x"]).to(device), clips[vid].to(device))

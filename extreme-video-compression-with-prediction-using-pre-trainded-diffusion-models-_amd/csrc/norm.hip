@@ -68,15 +68,22 @@ struct CoefArgs {
     float* coef_a; float* coef_s;
     unsigned* bound_bits;      // optional: atomicMax of the bit pattern of the largest {sum of squares} entry seen
     unsigned* events;          // optional: sticky range-event word (EVC_RANGE_*), OR-ed, never cleared by a kernel
+    unsigned* site_events;     // optional: this call's own word of a per-network site arena (&site_words[site]), OR-ed alike
 };
 
 // fp16-split arithmetic (EVC_ARITH_F16X3) scales GroupNorm-ed operands by 8: they must stay below 65504 / 8
 constexpr float F16_OPERAND_LIMIT = 65504.0f / 8.0f;
 constexpr unsigned NAN_BITS = 0x7fc00000u;      // as a bound word: "the tensor holds a non-finite element"
 
-__device__ __forceinline__ void raise_event(unsigned* events, unsigned bits) {
+__device__ __forceinline__ void raise_word(unsigned* w, unsigned bits) {
     // the word only ever gains bits: skip the atomic when they are already there (the common case is "nothing to report")
-    if (events && (__hip_atomic_load(events, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bits) != bits) atomicOr(events, bits);
+    if (w && (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bits) != bits) atomicOr(w, bits);
+}
+
+// Only ever called on the branches that report something: the site word costs a clean call nothing.
+__device__ __forceinline__ void raise_event(unsigned* events, unsigned* site_events, unsigned bits) {
+    raise_word(events, bits);
+    raise_word(site_events, bits);
 }
 
 // grid (groups, B), block 256: the (split, channel) moments of one group are summed in double by the whole
@@ -139,7 +146,7 @@ __global__ __launch_bounds__(256) void gn_coeffs_kernel(CoefArgs a) {
         const unsigned bits = bad ? NAN_BITS : __float_as_uint(gmx);
         if (bits > __hip_atomic_load(a.bound_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(a.bound_bits, bits);
     }
-    if (bad && tid == 0) raise_event(a.events, EVC_RANGE_NONFINITE);
+    if (bad && tid == 0) raise_event(a.events, a.site_events, EVC_RANGE_NONFINITE);
     sm = red[0][0] + red[0][1] + red[0][2] + red[0][3];
     sq = red[1][0] + red[1][1] + red[1][2] + red[1][3];
     const double n = (double)cpg * (double)a.HW;
@@ -172,9 +179,9 @@ __global__ __launch_bounds__(256) void gn_coeffs_kernel(CoefArgs a) {
         // on O(B*C) numbers here instead of on every element inside the convolution's K loop)
         wide |= !(fabsf(ca) * (xmax + fabsf(fmean)) + fabsf(add) < F16_OPERAND_LIMIT);
     }
-    if (!a.events) return;                    // uniform
+    if (!a.events && !a.site_events) return;  // uniform
     if (!__syncthreads_or(wide)) return;
-    if (bad) { if (tid == 0) raise_event(a.events, EVC_RANGE_NONFINITE); return; }
+    if (bad) { if (tid == 0) raise_event(a.events, a.site_events, EVC_RANGE_NONFINITE); return; }
     // Rare path.  The cheap test failed (e.g. a near-constant group: rstd is huge, |x - mean| tiny): bound |x - mean| per
     // element by the deviation of its own moment entry, sum (x - mean)^2 = sumsq - 2 mean sum + n mean^2 over the entry's
     // pixels, n <= ceil(HW / nsplit) (a larger n only loosens the bound), plus a rounding allowance.
@@ -209,7 +216,7 @@ __global__ __launch_bounds__(256) void gn_coeffs_kernel(CoefArgs a) {
         dev = fmaxf(fmaxf(red3[0][0], red3[0][1]), fmaxf(red3[0][2], red3[0][3]));
         amax = fmaxf(fmaxf(red3[1][0], red3[1][1]), fmaxf(red3[1][2], red3[1][3]));
         smax = fmaxf(fmaxf(red3[2][0], red3[2][1]), fmaxf(red3[2][2], red3[2][3]));
-        if (!(amax * sqrtf(fmaxf(dev, 0.f)) + smax < F16_OPERAND_LIMIT)) raise_event(a.events, EVC_RANGE_F16_OPERAND);
+        if (!(amax * sqrtf(fmaxf(dev, 0.f)) + smax < F16_OPERAND_LIMIT)) raise_event(a.events, a.site_events, EVC_RANGE_F16_OPERAND);
     }
 }
 
@@ -217,7 +224,8 @@ __global__ __launch_bounds__(256) void gn_coeffs_kernel(CoefArgs a) {
 // front of it (evc_moments_bound_f32).  grid (nsplit, B, ranges): range z = channels [c_begin + z*c_count, +c_count).
 __global__ __launch_bounds__(256) void moments_bound_kernel(const float* __restrict__ part, int nsplit, int C, int c_begin,
                                                             int c_count, unsigned* __restrict__ bound_bits,
-                                                            unsigned* __restrict__ events) {
+                                                            unsigned* __restrict__ events,
+                                                            unsigned* __restrict__ site_events) {
     const float* row = part + ((size_t)(blockIdx.y * nsplit + blockIdx.x) * C + c_begin + blockIdx.z * c_count) * 2;
     bound_bits += blockIdx.z;
     float mx = 0.f;
@@ -238,7 +246,7 @@ __global__ __launch_bounds__(256) void moments_bound_kernel(const float* __restr
         bad = redbad[0] | redbad[1] | redbad[2] | redbad[3];
         const unsigned bits = bad ? NAN_BITS : __float_as_uint(fmaxf(fmaxf(redmx[0], redmx[1]), fmaxf(redmx[2], redmx[3])));
         if (bits > __hip_atomic_load(bound_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(bound_bits, bits);
-        if (bad) raise_event(events, EVC_RANGE_NONFINITE);
+        if (bad) raise_event(events, site_events, EVC_RANGE_NONFINITE);
     }
 }
 
@@ -342,13 +350,36 @@ extern "C" int evc_gn_coeffs_f32(const float* part0, int nsplit0, int C0, const 
                                    ss_ld, row, coef_a, coef_s, nullptr, nullptr, stream);
 }
 
-extern "C" int evc_moments_bound_f32(const float* part, int nsplit, int C, int c_begin, int c_count, int n_ranges, int B,
-                                     unsigned* bound_bits, unsigned* events, void* stream) {
+extern "C" int evc_moments_bound_site_f32(const float* part, int nsplit, int C, int c_begin, int c_count, int n_ranges,
+                                          int B, unsigned* bound_bits, unsigned* events, unsigned* site_events, int site,
+                                          void* stream) {
     if (!part || !bound_bits || nsplit <= 0 || C <= 0 || B <= 0 || c_begin < 0 || c_count <= 0 || n_ranges <= 0 ||
-        c_begin + (long long)n_ranges * c_count > C)
+        c_begin + (long long)n_ranges * c_count > C || (site_events && site < 0))
         return EVC_EINVAL;
     hipLaunchKernelGGL(moments_bound_kernel, dim3(nsplit, B, n_ranges), dim3(256), 0, (hipStream_t)stream, part, nsplit, C,
-                       c_begin, c_count, bound_bits, events);
+                       c_begin, c_count, bound_bits, events, site_events ? site_events + site : nullptr);
+    return hipGetLastError() == hipSuccess ? EVC_OK : EVC_ELAUNCH;
+}
+
+extern "C" int evc_moments_bound_f32(const float* part, int nsplit, int C, int c_begin, int c_count, int n_ranges, int B,
+                                     unsigned* bound_bits, unsigned* events, void* stream) {
+    return evc_moments_bound_site_f32(part, nsplit, C, c_begin, c_count, n_ranges, B, bound_bits, events, nullptr, 0,
+                                      stream);
+}
+
+extern "C" int evc_gn_coeffs_bound_site_f32(const float* part0, int nsplit0, int C0, const float* part1, int nsplit1,
+                                            int C1, int B, int HW, int groups, float eps, int mode, const float* gamma,
+                                            const float* beta, const float* ss, int ss_ld, const int* row, float* coef_a,
+                                            float* coef_s, unsigned* bound_bits, unsigned* events, unsigned* site_events,
+                                            int site, void* stream) {
+    if (!part0 || C0 <= 0 || nsplit0 <= 0 || C1 < 0 || (C1 > 0 && (!part1 || nsplit1 <= 0))) return EVC_EINVAL;
+    if (B <= 0 || HW <= 0 || groups <= 0 || (C0 + C1) % groups != 0 || !coef_a || !coef_s) return EVC_EINVAL;
+    if (mode < 0 || mode > 2 || (mode == 1 && (!gamma || !beta)) || (mode == 2 && (!ss || ss_ld < 2 * (C0 + C1))))
+        return EVC_EINVAL;
+    if (site_events && site < 0) return EVC_EINVAL;
+    CoefArgs a{part0, nsplit0, C0, part1, nsplit1, C1, B, HW, groups, eps, mode, gamma, beta, ss, ss_ld, row,
+               coef_a, coef_s, bound_bits, events, site_events ? site_events + site : nullptr};
+    hipLaunchKernelGGL(gn_coeffs_kernel, dim3(groups, B), dim3(256), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? EVC_OK : EVC_ELAUNCH;
 }
 
@@ -356,14 +387,16 @@ extern "C" int evc_gn_coeffs_bound_f32(const float* part0, int nsplit0, int C0, 
                                        int B, int HW, int groups, float eps, int mode, const float* gamma,
                                        const float* beta, const float* ss, int ss_ld, const int* row, float* coef_a,
                                        float* coef_s, unsigned* bound_bits, unsigned* events, void* stream) {
-    if (!part0 || C0 <= 0 || nsplit0 <= 0 || C1 < 0 || (C1 > 0 && (!part1 || nsplit1 <= 0))) return EVC_EINVAL;
-    if (B <= 0 || HW <= 0 || groups <= 0 || (C0 + C1) % groups != 0 || !coef_a || !coef_s) return EVC_EINVAL;
-    if (mode < 0 || mode > 2 || (mode == 1 && (!gamma || !beta)) || (mode == 2 && (!ss || ss_ld < 2 * (C0 + C1))))
-        return EVC_EINVAL;
-    CoefArgs a{part0, nsplit0, C0, part1, nsplit1, C1, B, HW, groups, eps, mode, gamma, beta, ss, ss_ld, row,
-               coef_a, coef_s, bound_bits, events};
-    hipLaunchKernelGGL(gn_coeffs_kernel, dim3(groups, B), dim3(256), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? EVC_OK : EVC_ELAUNCH;
+    return evc_gn_coeffs_bound_site_f32(part0, nsplit0, C0, part1, nsplit1, C1, B, HW, groups, eps, mode, gamma, beta, ss,
+                                        ss_ld, row, coef_a, coef_s, bound_bits, events, nullptr, 0, stream);
+}
+
+extern "C" int evc_gn_coeffs_site_f32(const float* part0, int nsplit0, int C0, const float* part1, int nsplit1, int C1,
+                                      int B, int HW, int groups, float eps, int mode, const float* gamma,
+                                      const float* beta, const float* ss, int ss_ld, const int* row, float* coef_a,
+                                      float* coef_s, unsigned* events, unsigned* site_events, int site, void* stream) {
+    return evc_gn_coeffs_bound_site_f32(part0, nsplit0, C0, part1, nsplit1, C1, B, HW, groups, eps, mode, gamma, beta, ss,
+                                        ss_ld, row, coef_a, coef_s, nullptr, events, site_events, site, stream);
 }
 
 extern "C" int evc_affine_act_nhwc_f32(const float* x, float* y, const float* coef_a, const float* coef_s, int act,

@@ -15,6 +15,7 @@ import torch
 
 from . import lib as L
 from .elic import count_bits
+from .recovery import generate_with_recovery, recovery_mode, supports_recovery
 
 
 def all_generated_mask(frames=30, key=2, chunk=5):
@@ -25,11 +26,21 @@ def all_generated_mask(frames=30, key=2, chunk=5):
 
 
 class ClipDecoder:
-    def __init__(self, scorenet, elic_model, config, sampler, groups=1):
+    def __init__(self, scorenet, elic_model, config, sampler, groups=1, range_recovery=None, log=print):
         self.net, self.elic, self.config, self.sampler = scorenet, elic_model, config, sampler
         self.device = scorenet.device
         self.groups = groups          # concurrent clip groups (HIP streams) during generation
         self._stream_pool = []
+        # "layer": a chunk whose fp16-split operands may have left their range is regenerated with the layers that raised
+        # the event demoted to the bf16 split (recovery.py); "off" (default, or EVC_RANGE_RECOVERY): the caller's
+        # check_numerics stops the run.  Networks without event sites (UNetDDPM, pseudo-3-D) keep the "off" behaviour.
+        self.range_recovery = recovery_mode(range_recovery)
+        self.log = log
+        self.chunks = 0               # generated chunks so far (recovery log lines name them)
+        self.recovery_passes = []     # passes of every chunk recovery regenerated
+
+    def recovers(self):
+        return self.range_recovery == "layer" and supports_recovery(self.net)
 
     @torch.no_grad()
     def generate(self, cond_frames, noise_fn=None, generator=None, groups=None):
@@ -39,7 +50,42 @@ class ClipDecoder:
         ``groups`` > 1 splits the batch into that many clip groups that are sampled concurrently, each on its
         own HIP stream (clips are independent): idle CUs during one group's small kernels / partial tile rounds
         run another group's convolutions.  Per-clip results do not depend on the grouping when noise is injected
-        (``noise_fn`` is then called per group with the group's slice bounds)."""
+        (``noise_fn`` is then called per group with the group's slice bounds).
+
+        With range recovery on, the state of every noise source is saved first and restored before each regeneration:
+        ``generator`` (the per-group generators of ``groups`` > 1 are seeded from it, so they replay too), the device's
+        default generator when ``generator`` is None (exact for one group; several groups without a generator draw their
+        seeds from the host entropy pool and replay with new noise), and the network's ``cond_generator``; ``noise_fn``
+        must be deterministic (the policy sweep's counter-based noise is)."""
+        self.chunks += 1
+        if not self.recovers():
+            return self._generate(cond_frames, noise_fn, generator, groups)
+        net = self.net
+        saved_gen = generator.get_state() if generator is not None else None
+        saved_default = torch.cuda.get_rng_state(self.device) if generator is None and noise_fn is None else None
+        cgen = getattr(net, "cond_generator", None)
+        saved_cond = cgen.get_state() if cgen is not None else None
+
+        def restore():
+            if saved_gen is not None:
+                generator.set_state(saved_gen)
+            if saved_default is not None:
+                torch.cuda.set_rng_state(saved_default, self.device)
+            if saved_cond is not None:
+                cgen.set_state(saved_cond)
+
+        res = {}
+
+        def run():
+            res["frames"], res["raw"] = self._generate(cond_frames, noise_fn, generator, groups, with_raw=True)
+            return res["raw"]          # the sampler's output before the clamp of inverse_data_transform (clamping hides NaN)
+
+        _, passes, new = generate_with_recovery(run, restore, net, where=f"chunk {self.chunks}", log=self.log)
+        if new:
+            self.recovery_passes.append(passes)
+        return res["frames"]
+
+    def _generate(self, cond_frames, noise_fn, generator, groups, with_raw=False):
         from . import sampler as S
         cfg = self.config
         B, _, C, H, W = cond_frames.shape
@@ -92,9 +138,10 @@ class ClipDecoder:
             for st in streams:
                 main.wait_stream(st)
             pred = torch.cat([o[-1] for o in outs], dim=0).contiguous()
-        pred = L.scale_clamp(pred, 0.5, 0.5, (0.0, 1.0)) if cfg.data.rescaled else \
+        frames = L.scale_clamp(pred, 0.5, 0.5, (0.0, 1.0)) if cfg.data.rescaled else \
             L.scale_clamp(pred, 1.0, 0.0, (0.0, 1.0))                         # inverse_data_transform
-        return pred.reshape(B, cfg.data.num_frames, C, H, W)
+        frames = frames.reshape(B, cfg.data.num_frames, C, H, W)
+        return (frames, pred) if with_raw else frames
 
     def _streams(self, n):
         while len(self._stream_pool) < n:

@@ -94,6 +94,14 @@ HIP_SYMBOLS = {
                                         c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
     "evc_moments_bound_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "evc_gn_coeffs_site_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                       c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_int, c_void_p]),
+    "evc_gn_coeffs_bound_site_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                             c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "evc_moments_bound_site_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_int, c_void_p]),
     "evc_attention_f16x3_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                         c_float, c_void_p, c_void_p, c_void_p]),
     "evc_deconv5x5s2_phase_weights_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
@@ -319,7 +327,8 @@ def _events(device):
 def range_events(device=None, reset=False):
     """Bits raised so far on ``device`` (default: current): 0 = every fp16-split operand was provably in range and
     every tensor finite.  Synchronises the device.  RANGE_F16_OPERAND set means a trained checkpoint drives a normalised
-    activation towards fp16's limit: run that model with EVC_CONV_ARITH=bf16x6 (exact 3-way bf16 split, no range limit)."""
+    activation towards fp16's limit: run that model with EVC_CONV_ARITH=bf16x6 (exact 3-way bf16 split, no range limit),
+    or let the decoder move only the layers that raised it to that split (EVC_RANGE_RECOVERY=layer, ``site_events``)."""
     idx = torch.cuda.current_device() if device is None else torch.device(device).index
     w = _range_words.get(idx)
     if w is None:
@@ -328,6 +337,49 @@ def range_events(device=None, reset=False):
     if reset:
         w.zero_()
     return v
+
+
+class Site:
+    """Where a coefficient / bound call reports its range events besides the device word: word ``index`` of a network's
+    site arena ``words`` (``site_word_arena``).  ``quiet``: report to the site word only -- the network already moved that
+    site's consumers off the fp16 split, so the global word stays reserved for the sites that still matter."""
+    __slots__ = ("words", "index", "quiet")
+
+    def __init__(self, words, index, quiet=False):
+        self.words, self.index, self.quiet = words, int(index), bool(quiet)
+
+
+def site_word_arena(n, device):
+    """One zeroed int32 range-event word per event site of a network (include/evc_hip.h evc_*_site_f32).  Kept apart from
+    the per-forward bound arena: it is only cleared on demand (``site_events(net, reset=True)``)."""
+    return torch.zeros(max(1, int(n)), dtype=torch.int32, device=device)
+
+
+def site_events(net, reset=False):
+    """{site: EVC_RANGE_* bits} of the non-zero words of ``net``'s site arena, read with ONE device-to-host copy
+    (synchronises the device); ``reset`` zeroes the arena afterwards."""
+    w = net.site_words
+    v = w.cpu().tolist()
+    if reset:
+        w.zero_()
+    return {i: b for i, b in enumerate(v) if b}
+
+
+def _site_args(site, device):
+    """(events, site_events, index) pointers of a coefficient / bound call."""
+    if site is None:
+        return _word(_events(device)), None, 0
+    assert site.words.is_cuda and site.words.dtype == torch.int32 and 0 <= site.index < site.words.numel()
+    return (None if site.quiet else _word(_events(device))), c_void_p(site.words.data_ptr()), site.index
+
+
+def raise_range_events(bits, device=None):
+    """OR ``bits`` back into ``device``'s range-event word (a caller that cleared it to look at one piece of work restores
+    what was there before)."""
+    if bits:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        w = _events(dev)
+        w.bitwise_or_(int(bits))
 
 
 def im2col_nchw(x, KH, KW, stride, pad, ld_out, shift=None, scale=None):
@@ -399,10 +451,11 @@ def gpu_power_w(device=None):
     return None
 
 
-def gn_coeffs(parts, HW, groups, eps, mode=0, gamma=None, beta=None, ss=None, row=None, bound=None):
+def gn_coeffs(parts, HW, groups, eps, mode=0, gamma=None, beta=None, ss=None, row=None, bound=None, site=None):
     """parts: one or two partial-moment tensors (virtual concat). Returns (coef_a, coef_s), each (B, C).
     ``bound``: optional one-element int32 tensor (zeroed by the caller) raised to the bit pattern of the tensors'
-    element bound S (|x| <= sqrt(S)) -- what ``conv2d_nhwc(..., in_bound=)`` takes."""
+    element bound S (|x| <= sqrt(S)) -- what ``conv2d_nhwc(..., in_bound=)`` takes.  ``site``: a ``Site`` that also
+    receives this call's range events."""
     L = hip_lib()
     p0 = parts[0]
     p1 = parts[1] if len(parts) > 1 else None
@@ -412,11 +465,17 @@ def gn_coeffs(parts, HW, groups, eps, mode=0, gamma=None, beta=None, ss=None, ro
     ca = torch.empty((B, C), device=p0.device, dtype=torch.float32)
     cs = torch.empty((B, C), device=p0.device, dtype=torch.float32)
     ss_ld = 0 if ss is None else ss.stride(0)
-    _check(L.evc_gn_coeffs_bound_f32(fptr(p0), ns0, C0, fptr(p1), ns1, C1, B, HW, groups, eps, mode, fptr(gamma),
-                                     fptr(beta), c_void_p(ss.data_ptr()) if ss is not None else None, ss_ld,
-                                     fptr(row, torch.int32), fptr(ca), fptr(cs), _word(bound), _word(_events(p0.device)),
-                                     stream_ptr()),
-           "evc_gn_coeffs_bound_f32")
+    ssp = c_void_p(ss.data_ptr()) if ss is not None else None
+    if site is None:
+        _check(L.evc_gn_coeffs_bound_f32(fptr(p0), ns0, C0, fptr(p1), ns1, C1, B, HW, groups, eps, mode, fptr(gamma),
+                                         fptr(beta), ssp, ss_ld, fptr(row, torch.int32), fptr(ca), fptr(cs), _word(bound),
+                                         _word(_events(p0.device)), stream_ptr()),
+               "evc_gn_coeffs_bound_f32")
+    else:
+        _check(L.evc_gn_coeffs_bound_site_f32(fptr(p0), ns0, C0, fptr(p1), ns1, C1, B, HW, groups, eps, mode, fptr(gamma),
+                                              fptr(beta), ssp, ss_ld, fptr(row, torch.int32), fptr(ca), fptr(cs),
+                                              _word(bound), *_site_args(site, p0.device), stream_ptr()),
+               "evc_gn_coeffs_bound_site_f32")
     return ca, cs
 
 
@@ -428,11 +487,16 @@ def _word(t, n=1):
     return c_void_p(t.data_ptr())
 
 
-def moments_bound(part, c_begin, c_count, bound):
+def moments_bound(part, c_begin, c_count, bound, site=None):
     """Raise ``bound[z]`` to the element bound of channels [c_begin + z*c_count, + c_count) of a moments tensor
-    (B, ns, C, 2), for z < bound.numel()."""
+    (B, ns, C, 2), for z < bound.numel().  ``site``: as in ``gn_coeffs``."""
     B, ns, C, _ = part.shape
     n = bound.numel()
+    if site is not None:
+        _check(hip_lib().evc_moments_bound_site_f32(fptr(part), ns, C, c_begin, c_count, n, B, _word(bound, n),
+                                                    *_site_args(site, part.device), stream_ptr()),
+               "evc_moments_bound_site_f32")
+        return
     _check(hip_lib().evc_moments_bound_f32(fptr(part), ns, C, c_begin, c_count, n, B, _word(bound, n),
                                            _word(_events(part.device)), stream_ptr()),
            "evc_moments_bound_f32")

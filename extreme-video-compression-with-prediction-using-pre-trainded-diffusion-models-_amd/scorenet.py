@@ -85,6 +85,32 @@ def build_program(d):
     return mods
 
 
+def range_sites(program, cond_emb=False):
+    """Event sites of one forward, in program order (include/evc_hip.h evc_*_site_f32): every coefficient / bound call whose
+    range events guard fp16-split work, with the consumers that move to the exact bf16 split when the site is demoted
+    (``ScoreNet.demote``).  A consumer is (module index, weight key), or (module index, "attention") for the fp16-split
+    attention kernel.  ``tag`` says which call of the module it is; ``name`` is the reference's module name
+    (``all_modules.<i>``, one higher from index 2 on with cond_emb) of what gets demoted."""
+    sites = []
+    for i, m in enumerate(program):
+        n = f"all_modules.{i + (1 if cond_emb and i >= 2 else 0)}"
+        k = m["kind"]
+        if k == "res":
+            has_skip = m["cin"] != m["cout"] or m["up"] or m["down"]
+            sites.append(dict(tag="res0", module=i, name=n + ".Conv_0", consumers=[(i, "w0")]))
+            # Conv_2 rides in Conv_1's launch when fused (f16x3 row-reuse kernel only): they move together
+            sites.append(dict(tag="res1", module=i, name=n + ".Conv_1", consumers=[(i, "w1")] + ([(i, "w2")] if has_skip else [])))
+        elif k == "attn":
+            sites.append(dict(tag="attn_norm", module=i, name=n + ".NIN_0-2", consumers=[(i, "wqkv")]))
+            sites.append(dict(tag="attn_qkv", module=i, name=n + ".NIN_3", consumers=[(i, "attention"), (i, "wo")]))
+        elif k == "norm":
+            sites.append(dict(tag="norm", module=i, name=f"all_modules.{i + 1 + (1 if cond_emb else 0)}",
+                              consumers=[(i + 1, "w")]))
+    for j, st in enumerate(sites):
+        st["site"] = j
+    return sites
+
+
 class _Act:
     """An NHWC activation with lazily computed, cached per-channel moments."""
     __slots__ = ("t", "_stats")
@@ -97,6 +123,11 @@ class _Act:
         if self._stats is None:
             self._stats = L.chan_stats(self.t)
         return self._stats
+
+
+def _f16_only(w_packed, bound):
+    """An element bound is an operand of the fp16-split kernels only (a demoted, bf16x6 convolution takes none)."""
+    return bound if L.packed_arith(w_packed) == L.ARITH_F16X3 else None
 
 
 def _pad16(c):
@@ -171,8 +202,9 @@ class ScoreNet(DdpmWrapper):
 
     SPADE = False      # scorenet_spade.SpadeScoreNet: conditioning through SPADE act-norms (model.spade: true)
     ARCH = "unetmore"  # scorenet_pseudo3d.Pseudo3dScoreNet: "unetmorepseudo3d"
+    RANGE_SITES = True  # per-site range events and ``demote`` (range_sites); the pseudo-3-D networks use no fp16 split
 
-    def __init__(self, config, state_dict, device="cuda", prefix="", preactivate=False, use_graphs=False):
+    def __init__(self, config, state_dict, device="cuda", prefix="", preactivate=False, use_graphs=False, demote=()):
         L.hip_lib()   # fail loudly before touching anything else
         # preactivate=False: AdaGN + SiLU is fused into the 3x3 convolutions' operand load (evaluated once per
         # filter tap, costs MFMA issue slots); True: applied once per tensor by evc_affine_act_nhwc_f32 and the
@@ -200,7 +232,17 @@ class ScoreNet(DdpmWrapper):
         self.program = self._build_program()
         if self.SPADE:     # the conditioning frames do not enter through the input (ncsnpp_more.py:519, :593-594)
             self.program[2]["cin"] = self.d.channels * self.d.num_frames
+        self._wsrc = {}          # (module, key) -> (fp32 weight, pad_ci) of every fp16-split pack: what demote() repacks
         self._load(state_dict, prefix + "unet.all_modules.")
+        # range-event sites (range_sites) and their arena; demotion is sticky for the network's lifetime
+        self.sites = range_sites(self.program, self.cond_emb) if self.RANGE_SITES else []
+        self.site_words = L.site_word_arena(len(self.sites), self.device)
+        self._demoted = set()
+        self._attn_f32 = set()   # attention modules on the range-free f32 kernel
+        self._unfused = set()    # res-blocks whose Conv_2 may not ride in Conv_1's launch
+        self._site_of = {}
+        self._set_site_args()
+        self.demote_seconds = 0.0
         self._rows = {}          # label value -> row of the AdaGN table
         self._row_tensors = {}   # (row, B) -> int32 device tensor
         # AdaGN table with spare capacity: captured graphs hold pointers into it, so it only moves (and the
@@ -225,6 +267,58 @@ class ScoreNet(DdpmWrapper):
         self._bounds_by_stream = {}      # concurrent clip groups run forwards on their own streams: one arena each
         self._bounds = None
         self._bound_next = 0
+        if demote:
+            self.demote(demote)
+
+    # ---- range-event sites ---------------------------------------------------------------------
+    def _set_site_args(self):
+        self._site_of = {(st["tag"], st["module"]): L.Site(self.site_words, st["site"], quiet=st["site"] in self._demoted)
+                         for st in self.sites}
+
+    def _site(self, tag, i):
+        return self._site_of.get((tag, i))
+
+    def _site_ids(self, sites):
+        by_name = {st["name"]: st["site"] for st in self.sites}
+        out = []
+        for s in sites:
+            k = by_name.get(s) if isinstance(s, str) else int(s)
+            if k is None or not 0 <= k < len(self.sites):
+                raise KeyError(f"no range-event site {s!r} in this network")
+            out.append(k)
+        return out
+
+    def demote(self, sites):
+        """Move the fp16-split consumers of ``sites`` (indices or names of ``self.sites``) to the exact bf16 split: their
+        weights are repacked for ARITH_BF16X6, a demoted attention site switches that block to the range-free f32
+        attention kernel, a demoted res-block stops fusing its skip convolution into Conv_1 (the fused form exists on the
+        fp16-split kernel only), and the captured HIP graphs (pointers to the old packs) are dropped.  A demoted site
+        still runs its range test but reports to its own site word only.  Sticky.  Returns the newly demoted sites."""
+        import time
+        new = [k for k in dict.fromkeys(self._site_ids(sites)) if k not in self._demoted]
+        if not new:
+            return []
+        t0 = time.perf_counter()
+        for k in new:
+            for i, key in self.sites[k]["consumers"]:
+                if key == "attention":
+                    self._attn_f32.add(i)
+                    continue
+                if key in ("w1", "w2"):
+                    self._unfused.add(i)
+                if L.packed_arith(self.w[i][key]) == L.ARITH_F16X3:
+                    w, pad_ci = self._wsrc[(i, key)]
+                    self.w[i][key] = self._repack(w, pad_ci, L.ARITH_BF16X6)
+            self._demoted.add(k)
+        self._set_site_args()
+        self._graphs.clear()
+        torch.cuda.synchronize(self.device)
+        self.demote_seconds += time.perf_counter() - t0
+        return new
+
+    def demoted_sites(self):
+        """{site: module name} of the demoted sites."""
+        return {k: self.sites[k]["name"] for k in sorted(self._demoted)}
 
     # ------------------------------------------------------------------------------------------
     def _build_program(self):
@@ -240,12 +334,21 @@ class ScoreNet(DdpmWrapper):
     def _pack_conv(self, w, pad_ci=None, bounded=False):
         """``bounded``: the convolution's input is GroupNorm-normalised / activated (O(1)), so the fp16-split
         arithmetic applies; raw residual-stream inputs keep the bf16 split (no range assumption)."""
+        return self._repack(w, pad_ci, L.bounded_arith() if bounded else L.default_arith())
+
+    def _repack(self, w, pad_ci, arith):
         w = self._dev(w)
         if pad_ci is not None and pad_ci != w.shape[1]:
             wp = torch.zeros((w.shape[0], pad_ci, w.shape[2], w.shape[3]), device=self.device)
             wp[:, :w.shape[1]] = w
             w = wp
-        return L.conv_pack_weights(w, L.bounded_arith() if bounded else L.default_arith())
+        return L.conv_pack_weights(w, arith)
+
+    def _pack_site(self, i, key, w, pad_ci=None):
+        """A convolution guarded by a range-event site: packed like ``_pack_conv(bounded=True)``, its fp32 weight kept
+        (a reference to the state-dict tensor) so that ``demote`` can repack it."""
+        self._wsrc[(i, key)] = (w, pad_ci)
+        return self._pack_conv(w, pad_ci, bounded=True)
 
     def _load(self, sd, pre):
         g = lambda name: sd[name]
@@ -264,7 +367,8 @@ class ScoreNet(DdpmWrapper):
                                  co=w.shape[0])
             elif k in ("conv_in", "conv_out"):
                 w = g(n + ".weight")     # conv_out reads the final GroupNorm + SiLU; conv_in the raw network input
-                self.w[i] = dict(w=self._pack_conv(w, _pad16(w.shape[1]), bounded=(k == "conv_out")),
+                self.w[i] = dict(w=(self._pack_site(i, "w", w, _pad16(w.shape[1])) if k == "conv_out" else
+                                    self._pack_conv(w, _pad16(w.shape[1]))),
                                  b=self._dev(g(n + ".bias")),
                                  co=w.shape[0], cin_pad=_pad16(w.shape[1]))
             elif k == "res":
@@ -276,12 +380,12 @@ class ScoreNet(DdpmWrapper):
                     off += dw.shape[0]
                     self._load_actnorm(e, j, f"{n}.{key}", g)
                 # Conv_0 / Conv_1 read AdaGN + SiLU outputs (directly or through the FIR resampler): O(1) operands
-                e["w0"] = self._pack_conv(g(n + ".Conv_0.weight"), bounded=True); e["b0"] = self._dev(g(n + ".Conv_0.bias"))
-                e["w1"] = self._pack_conv(g(n + ".Conv_1.weight"), bounded=True); e["b1"] = self._dev(g(n + ".Conv_1.bias"))
+                e["w0"] = self._pack_site(i, "w0", g(n + ".Conv_0.weight")); e["b0"] = self._dev(g(n + ".Conv_0.bias"))
+                e["w1"] = self._pack_site(i, "w1", g(n + ".Conv_1.weight")); e["b1"] = self._dev(g(n + ".Conv_1.bias"))
                 if m["cin"] != m["cout"] or m["up"] or m["down"]:
                     # 1x1 skip convolution on the raw residual stream: fp16 split too, scaled by the element bound that
                     # the block's own GroupNorm moments give (gn_coeffs(..., bound=))
-                    e["w2"] = self._pack_conv(g(n + ".Conv_2.weight"), bounded=True); e["b2"] = self._dev(g(n + ".Conv_2.bias"))
+                    e["w2"] = self._pack_site(i, "w2", g(n + ".Conv_2.weight")); e["b2"] = self._dev(g(n + ".Conv_2.bias"))
                     e["b12"] = (e["b1"] + e["b2"]).contiguous()      # bias of Conv_1 with Conv_2 fused into it
                 self.w[i] = e
             elif k == "attn":
@@ -290,10 +394,10 @@ class ScoreNet(DdpmWrapper):
                 wqkv = torch.cat([w.t() for w in ws[:3]], 0)[:, :, None, None]
                 self.w[i] = dict(gamma=self._dev(g(n + ".GroupNorm_0.weight")),
                                  beta=self._dev(g(n + ".GroupNorm_0.bias")),
-                                 wqkv=self._pack_conv(wqkv, bounded=True),     # input: affine GroupNorm
+                                 wqkv=self._pack_site(i, "wqkv", wqkv),     # input: affine GroupNorm
                                  bqkv=self._dev(torch.cat(bs[:3], 0)),
                                  # output projection: |attention output| <= max |v|, bounded through v's moments
-                                 wo=self._pack_conv(ws[3].t()[:, :, None, None], bounded=True), bo=self._dev(bs[3]))
+                                 wo=self._pack_site(i, "wo", ws[3].t()[:, :, None, None]), bo=self._dev(bs[3]))
             elif k == "norm":
                 self.w[i] = self._load_final_norm(n, g)
         self.ss_total = off
@@ -357,11 +461,11 @@ class ScoreNet(DdpmWrapper):
         return t
 
     # ------------------------------------------------------------------------------------------
-    def _adagn(self, parts, hw, ch, seg, rows, bound=None):
+    def _adagn(self, parts, hw, ch, seg, rows, bound=None, site=None):
         off, c = seg
         assert c == ch
         return L.gn_coeffs(parts, hw, num_groups(ch), 1e-5, mode=2, ss=self._table[:, off:off + 2 * c], row=rows,
-                           bound=bound)
+                           bound=bound, site=site)
 
     def _side_stream(self, main):
         """The side stream paired with a main stream (one per concurrent clip group / capture)."""
@@ -385,7 +489,7 @@ class ScoreNet(DdpmWrapper):
         B, H, W, _ = x.t.shape
         parts = [x.stats()] + ([skip.stats()] if skip is not None else [])
         xbound = self._bound_slot() if "w2" in e else None     # bounds x (and skip): also FIR(x), whose taps sum to 1
-        coef0 = self._adagn(parts, H * W, m["cin"], e["ss0"], rows, bound=xbound)
+        coef0 = self._adagn(parts, H * W, m["cin"], e["ss0"], rows, bound=xbound, site=self._site("res0", i))
         fir = None
         if m["up"] or m["down"]:
             fir = (FIR_K * 4.0, 2, 1, (2, 1)) if m["up"] else (FIR_K, 1, 2, (1, 1))   # upsample_2d: gain factor**2, pad (2, 1)
@@ -398,11 +502,12 @@ class ScoreNet(DdpmWrapper):
             if fir is not None:
                 src, src1 = L.upfirdn2d_nhwc(x.t, *fir), None
             if "w2" in e:
-                return L.conv2d_nhwc(src, e["w2"], m["cout"], 1, 1, bias=e["b2"], src1=src1, in_bound=xbound, out=out)
+                return L.conv2d_nhwc(src, e["w2"], m["cout"], 1, 1, bias=e["b2"], src1=src1, in_bound=_f16_only(e["w2"], xbound),
+                                     out=out)
             return src
 
         Ho, Wo = (2 * H, 2 * W) if m["up"] else ((H // 2, W // 2) if m["down"] else (H, W))
-        fuse = self.fuse_skip and "w2" in e and not self.preactivate and \
+        fuse = self.fuse_skip and "w2" in e and not self.preactivate and i not in self._unfused and \
             L.conv_fused_1x1_supported(B, Ho, Wo, m["cout"], m["cout"], L.packed_arith(e["w1"]))
         # The x-branch only depends on the block input: with `overlap_skip` it runs on a side stream while the main stream
         # does the h-branch (FIR, Conv_0, its moments), so its small latency-bound launches (the 1x1 convolution, its
@@ -436,7 +541,7 @@ class ScoreNet(DdpmWrapper):
             h1 = _Act(*L.conv2d_nhwc(x.t, e["w0"], m["cout"], 3, 3, bias=e["b0"], src1=s1, coef=coef0, act_in=L.ACT_SILU,
                                      want_stats=True))
         H1, W1 = h1.t.shape[1], h1.t.shape[2]
-        coef1 = self._adagn([h1.stats()], H1 * W1, m["cout"], e["ss1"], rows)
+        coef1 = self._adagn([h1.stats()], H1 * W1, m["cout"], e["ss1"], rows, site=self._site("res1", i))
         if side is None:
             if fuse:
                 xs = L.upfirdn2d_nhwc(x.t, *fir) if fir is not None else None
@@ -463,7 +568,8 @@ class ScoreNet(DdpmWrapper):
         B, H, W, C = x.t.shape
         hd = self.d.n_head_channels
         heads = 1 if C < hd else C // hd
-        coef = L.gn_coeffs([x.stats()], H * W, num_groups(C), 1e-6, mode=1, gamma=e["gamma"], beta=e["beta"])
+        coef = L.gn_coeffs([x.stats()], H * W, num_groups(C), 1e-6, mode=1, gamma=e["gamma"], beta=e["beta"],
+                           site=self._site("attn_norm", i))
         qkvb = self._bound_slot(3)
         if qkvb is None:
             obound = None
@@ -472,9 +578,9 @@ class ScoreNet(DdpmWrapper):
             # element bounds of q, k, v from the projection's fused moments (one small launch); the attention output is
             # a convex combination of value rows, so max |o| <= max |v|: v's bound also serves the output projection
             qkv, qst = L.conv2d_nhwc(x.t, e["wqkv"], 3 * C, 1, 1, bias=e["bqkv"], coef=coef, want_stats=True)
-            L.moments_bound(qst, 0, C, qkvb)
-            obound = qkvb[2:3]
-        o = L.attention(qkv.view(B, H * W, 3 * C), C, heads, bounds=qkvb)
+            L.moments_bound(qst, 0, C, qkvb, site=self._site("attn_qkv", i))
+            obound = _f16_only(e["wo"], qkvb[2:3])
+        o = L.attention(qkv.view(B, H * W, 3 * C), C, heads, bounds=None if i in self._attn_f32 else qkvb)
         return _Act(*L.conv2d_nhwc(o.view(B, H, W, C), e["wo"], C, 1, 1, bias=e["bo"], res=x.t,
                                    out_scale=INV_SQRT2, want_stats=True, in_bound=obound))
 
@@ -546,7 +652,8 @@ class ScoreNet(DdpmWrapper):
         """Final GroupNorm + SiLU fused into the output convolution's load (ncsnpp_more.py:380-388)."""
         e = self.w[i]
         B, H, W, C = h.t.shape
-        coef = L.gn_coeffs([h.stats()], H * W, num_groups(C), 1e-5, mode=1, gamma=e["gamma"], beta=e["beta"])
+        coef = L.gn_coeffs([h.stats()], H * W, num_groups(C), 1e-5, mode=1, gamma=e["gamma"], beta=e["beta"],
+                           site=self._site("norm", i))
         co = self.program[i + 1]["cout"]
         out = torch.empty((B, H, W, _pad16(co)), device=h.t.device, dtype=torch.float32)
         L.conv2d_nhwc(h.t, self.w[i + 1]["w"], co, 3, 3, bias=self.w[i + 1]["b"], coef=coef, act_in=L.ACT_SILU, out=out)

@@ -87,6 +87,7 @@ class Pseudo3dScoreNet(ScoreNet):
     """HIP implementation of ``UNetMore_DDPM`` with ``arch: unetmorepseudo3d`` (eval mode, dropout 0)."""
 
     ARCH = "unetmorepseudo3d"
+    RANGE_SITES = False
 
     def __init__(self, config, state_dict, device="cuda", prefix="", use_graphs=False, **_):
         super().__init__(config, state_dict, device=device, prefix=prefix, preactivate=False, use_graphs=use_graphs)

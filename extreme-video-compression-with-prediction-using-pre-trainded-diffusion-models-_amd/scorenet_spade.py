@@ -24,7 +24,7 @@ Parity: ``tests/test_gpu_scorenet.py::test_spade_*`` against ``tests/golden/forw
 import torch
 
 from . import lib as L
-from .scorenet import FIR_K, INV_SQRT2, ScoreNet, _Act, _pad16, num_groups
+from .scorenet import FIR_K, INV_SQRT2, ScoreNet, _Act, _f16_only, _pad16, num_groups
 
 
 class SpadeScoreNet(ScoreNet):
@@ -112,11 +112,11 @@ class SpadeScoreNet(ScoreNet):
         self._set_cond(cond)
         return L.pack_nchw_to_nhwc(x, None, cin_pad)
 
-    def _actnorm(self, key, sp, parts, seg, rows, bound=None):
+    def _actnorm(self, key, sp, parts, seg, rows, bound=None, site=None):
         """get_act_norm.forward, norm == 'spade' (layerspp.py:518-549) on a (virtual) concat of NHWC parts."""
         B, H, W, _ = parts[0].t.shape
         ch = sp["ch"]
-        coef = L.gn_coeffs([p.stats() for p in parts], H * W, num_groups(ch), 1e-6, mode=0, bound=bound)
+        coef = L.gn_coeffs([p.stats() for p in parts], H * W, num_groups(ch), 1e-6, mode=0, bound=bound, site=site)
         maps = self._map(key, sp, B, H, W)
         ss = None
         if seg is not None:
@@ -136,25 +136,25 @@ class SpadeScoreNet(ScoreNet):
         e = self.w[i]
         parts = [x] + ([skip] if skip is not None else [])
         xbound = self._bound_slot() if "w2" in e else None
-        h = self._actnorm((i, 0), e["sp0"], parts, e["ss0"], rows, bound=xbound)
+        h = self._actnorm((i, 0), e["sp0"], parts, e["ss0"], rows, bound=xbound, site=self._site("res0", i))
         fir = None
         if m["up"] or m["down"]:
             fir = (FIR_K * 4.0, 2, 1, (2, 1)) if m["up"] else (FIR_K, 1, 2, (1, 1))
             h = L.upfirdn2d_nhwc(h, *fir)
         h1 = _Act(*L.conv2d_nhwc(h, e["w0"], m["cout"], 3, 3, bias=e["b0"], want_stats=True))
-        h1a = self._actnorm((i, 1), e["sp1"], [h1], e["ss1"], rows)
+        h1a = self._actnorm((i, 1), e["sp1"], [h1], e["ss1"], rows, site=self._site("res1", i))
         src, src1 = x.t, (None if skip is None else skip.t)
         if fir is not None:
             src, src1 = L.upfirdn2d_nhwc(x.t, *fir), None
         xs = src
         if "w2" in e:
-            xs = L.conv2d_nhwc(src, e["w2"], m["cout"], 1, 1, bias=e["b2"], src1=src1, in_bound=xbound)
+            xs = L.conv2d_nhwc(src, e["w2"], m["cout"], 1, 1, bias=e["b2"], src1=src1, in_bound=_f16_only(e["w2"], xbound))
         return _Act(*L.conv2d_nhwc(h1a, e["w1"], m["cout"], 3, 3, bias=e["b1"], res=xs, out_scale=INV_SQRT2,
                                    want_stats=True))
 
     def _final(self, i, h):
         """Final SPADE act-norm (no time embedding) + output convolution (ncsnpp_more.py:700-707)."""
-        act = self._actnorm((i, 0), self.w[i]["sp0"], [h], None, None)
+        act = self._actnorm((i, 0), self.w[i]["sp0"], [h], None, None, site=self._site("norm", i))
         B, H, W, _ = act.shape
         co = self.program[i + 1]["cout"]
         out = torch.empty((B, H, W, _pad16(co)), device=self.device, dtype=torch.float32)

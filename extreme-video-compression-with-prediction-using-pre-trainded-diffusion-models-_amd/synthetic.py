@@ -9,6 +9,7 @@ reference-layout checkpoints with seeded random weights, and smooth random 30-fr
 * clips: ``uint8 (n, 30, 3, 128, 128)`` low-pass filtered noise with slow motion, shaped like ``city_bonn.npy``.
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -118,6 +119,20 @@ def diffusion_state_dict(config, seed):
         else:
             a = rng.standard_normal(shape, dtype=np.float32) / np.float32(math.sqrt(int(np.prod(shape[1:]))))
         sd[name] = torch.from_numpy(a)
+    return inflate_adagn(sd, os.environ.get("EVC_SYNTHETIC_ADAGN_SCALE", ""))
+
+
+def inflate_adagn(sd, spec):
+    """Stand-in for a trained checkpoint with large AdaGN rows: ``spec`` = "all_modules.<i>.actnorm<j>=<factor>[,...]"
+    multiplies that act-norm's Dense_0 (weight and bias: both the scale and the shift of its rows) by factor.  Read from
+    EVC_SYNTHETIC_ADAGN_SCALE by ``diffusion_state_dict`` (the range-recovery tests drive the CLI with it)."""
+    for item in filter(None, (t.strip() for t in spec.split(","))):
+        mod, factor = item.split("=")
+        keys = [f"unet.{mod}.Dense_0.weight", f"unet.{mod}.Dense_0.bias"]
+        if not all(k in sd for k in keys):
+            raise KeyError(f"EVC_SYNTHETIC_ADAGN_SCALE: no act-norm {mod!r} in the synthetic state dict")
+        for k in keys:
+            sd[k] = sd[k] * float(factor)
     return sd
 
 

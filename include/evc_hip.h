@@ -104,7 +104,9 @@ int evc_gn_coeffs_f32(const float* part0, int nsplit0, int C0, const float* part
  *   EVC_RANGE_NONFINITE    a tensor's moments are not finite: it holds a NaN or an infinity;
  *   EVC_RANGE_F16_OPERAND  for some channel |coef_a| * max|x| + |coef_s| >= 65504 / 8: a GroupNorm-ed (and activated,
  *                          |SiLU(v)| <= |v|) operand element MAY leave fp16's range.  Zero means none can (a sufficient
- *                          condition).  Remedy: EVC_ARITH_BF16X6 for that model (host: EVC_CONV_ARITH=bf16x6). */
+ *                          condition).  Remedy: EVC_ARITH_BF16X6 for that model (host: EVC_CONV_ARITH=bf16x6), or for
+ *                          the consumers of the site that raised it only (the _site_ forms below; host:
+ *                          EVC_RANGE_RECOVERY=layer). */
 #define EVC_RANGE_NONFINITE 1u
 #define EVC_RANGE_F16_OPERAND 2u
 
@@ -121,6 +123,28 @@ int evc_gn_coeffs_bound_f32(const float* part0, int nsplit0, int C0, const float
  * projection feeding attention has three). */
 int evc_moments_bound_f32(const float* part, int nsplit, int C, int c_begin, int c_count, int n_ranges, int B,
                           unsigned* bound_bits, unsigned* events, void* stream);
+
+/* Per-site attribution of the range events.  An event SITE is one of these calls inside a network's forward (the
+ * caller numbers them; each guards the fp16-split consumers of the tensor it bounds).  The _site_ forms take the caller's
+ * site arena `site_events` (one word per site, zeroed by the caller, never cleared by a kernel) and the call's index
+ * `site`, and on exactly the conditions above OR the same EVC_RANGE_* bits into BOTH `events` and site_events[site]
+ * (either may be NULL; site_events NULL makes them the plain forms).  The extra atomic sits on the branches that already
+ * raise: a clean call does the same work as the plain form.  With `events` NULL and site_events set the call still runs
+ * the range test but reports to its site word only (a caller that already moved the site's consumers off the fp16 split
+ * keeps the global word for the sites that still matter).
+ *   evc_gn_coeffs_site_f32:       evc_gn_coeffs_f32 + the event words (no element bound);
+ *   evc_gn_coeffs_bound_site_f32: evc_gn_coeffs_bound_f32 + the site word;
+ *   evc_moments_bound_site_f32:   evc_moments_bound_f32 + the site word (EVC_RANGE_NONFINITE only, as the plain form). */
+int evc_gn_coeffs_site_f32(const float* part0, int nsplit0, int C0, const float* part1, int nsplit1, int C1, int B,
+                           int HW, int groups, float eps, int mode, const float* gamma, const float* beta,
+                           const float* ss, int ss_ld, const int* row, float* coef_a, float* coef_s, unsigned* events,
+                           unsigned* site_events, int site, void* stream);
+int evc_gn_coeffs_bound_site_f32(const float* part0, int nsplit0, int C0, const float* part1, int nsplit1, int C1, int B,
+                                 int HW, int groups, float eps, int mode, const float* gamma, const float* beta,
+                                 const float* ss, int ss_ld, const int* row, float* coef_a, float* coef_s,
+                                 unsigned* bound_bits, unsigned* events, unsigned* site_events, int site, void* stream);
+int evc_moments_bound_site_f32(const float* part, int nsplit, int C, int c_begin, int c_count, int n_ranges, int B,
+                               unsigned* bound_bits, unsigned* events, unsigned* site_events, int site, void* stream);
 
 /* y = act(x*coef_a[b][c] + coef_s[b][c]) elementwise on NHWC: the stand-alone form of the fused load.  One pass per
  * tensor instead of once per filter tap inside the convolution (SiLU costs MFMA issue slots there; HBM is cheap).
