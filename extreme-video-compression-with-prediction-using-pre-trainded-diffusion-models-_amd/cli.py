@@ -10,7 +10,9 @@ the DEFAULT whenever a perceptual metric is available -- ``--metric`` (weight fi
 ``pkg.module:callable``) or LPIPS weight files found where the reference keeps them (``find_lpips_weights``); without one
 the explicit fallback ``mask`` (fixed transmit mask) runs and the CLI says so; ``psnr`` is the reference's own
 ``decide_5to5`` (city_sender.py:353-374); ``--synthetic`` builds seeded stand-ins when checkpoints / data are
-absent.  ``--gpus N`` (or ``torch.distributed.run``) block-shards the video range over N ranks, one GPU each.
+absent.  ``--fvd`` (or ``i3d_pretrained_400.pt`` found where the reference keeps it, ``find_i3d_weights``) adds the
+reference's third per-job number, the FVD of the decoded clip against the original (city_sender.py:575-589), computed by the
+HIP I3D network (fvd.py) and saved as ``fvd_<idx>.npy``.  ``--gpus N`` (or ``torch.distributed.run``) block-shards the video range over N ranks, one GPU each.
 """
 import argparse
 import os
@@ -80,7 +82,24 @@ def build_parser():
                    help="layer: when a chunk raises an fp16-split range event, demote only the layers that raised it to the "
                         "bf16x6 split and regenerate the chunk with the same noise (default: EVC_RANGE_RECOVERY, else off: "
                         "the run stops with the remedy)")
+    p.add_argument("--fvd", type=str, default=None,
+                   help="i3d_pretrained_400.pt (InceptionI3d state dict): report each job's FVD against the original clip "
+                        "(city_sender.py:575-589) and save fvd_<idx>.npy; default: the file under models/fvd/, "
+                        "fvd_utils/models/fvd/ or benchmark/fvd_utils/models/fvd/ when present, else FVD is skipped")
     return p
+
+
+def resolve_fvd(args, log=print):
+    """The I3D weight file of this run's FVD, or None (FVD skipped, said once)."""
+    from .fvd import WEIGHT_DIRS, WEIGHT_FILE, find_i3d_weights
+    path = args.fvd or find_i3d_weights()
+    if path is None:
+        log(f"FVD: skipped (no --fvd and no {WEIGHT_FILE} under {', '.join(d + '/' for d in WEIGHT_DIRS)})")
+    elif not os.path.isfile(path):
+        sys.exit(f"--fvd {path}: no such file")
+    else:
+        log(f"FVD: I3D weights {path}")
+    return path
 
 
 def find_lpips_weights(roots=(".",)):
@@ -172,6 +191,7 @@ def main(argv=None):
     from .scorenet import build_score_network
 
     resolve_policy(args, log=lambda m: print(m, flush=True))
+    fvd_path = resolve_fvd(args, log=lambda m: print(m, flush=True))
     cfg, raw = C.load_config(args.config, args.config_mod)
     if args.subsample is not None:
         cfg.sampling.subsample = args.subsample
@@ -180,6 +200,10 @@ def main(argv=None):
     if args.gpus > 1 and world != args.gpus:
         sys.exit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     L.hip_lib()
+    i3d = None
+    if fvd_path:
+        from . import fvd as FV
+        i3d = FV.I3d.from_file(fvd_path, device=device)
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     vf = os.path.join(args.exp, "video_samples", args.video_folder)
@@ -228,11 +252,30 @@ def main(argv=None):
     t_start = time.time()
     vids = list(range(args.start_idx + lo, args.start_idx + hi))
 
-    def report(vid, q, thr, x, gt, bits, d, store):
+    gt_feats, fvd_store = {}, {}
+
+    def job_fvds(jobs):
+        """FVD of each decoded clip against its video's original, as city_sender.py:575-577 computes it: calculate_fvd of
+        x_ge.repeat(2) against x_gt.repeat(2).  jobs: [(vid, x, gt)] numpy (30, 3, H, W).  I3D runs once per original video
+        and once per decoded clip, all clips of the call batched."""
+        if i3d is None:
+            return [None] * len(jobs)
+        new = {vid: gt for vid, _, gt in jobs if vid not in gt_feats}
+        if new:
+            for vid, f in zip(new, i3d(torch.from_numpy(np.stack(list(new.values())))).double().cpu().numpy()):
+                gt_feats[vid] = f
+        fx = i3d(torch.from_numpy(np.stack([x for _, x, _ in jobs]))).double().cpu().numpy()
+        return [FV.frechet_distance(np.stack([f, f]), np.stack([gt_feats[vid], gt_feats[vid]]))
+                for f, (vid, _, _) in zip(fx, jobs)]
+
+    def report(vid, q, thr, x, gt, bits, d, store, fvd=None):
         bpp = sum(bits) / 128 / 128 / 30
         ps = [cal_psnr(x[i], gt[i]) for i in range(30)]
         print(f"[rank {rank}] video {vid} q{q} thr {thr:.2f}: d={[int(v) for v in d[:30]]} BPP {bpp:.5f} PSNR {np.mean(ps):.3f}",
               flush=True)
+        if fvd is not None:
+            print(f"[rank {rank}] video {vid} q{q} thr {thr:.2f}: FVD: {fvd:f}", flush=True)
+            fvd_store.setdefault(vid, []).append(fvd)
         store.setdefault(vid, ([], []))
         store[vid][0].append(ps); store[vid][1].append(bpp)
         g = np.concatenate(list(gt.transpose(0, 2, 3, 1)), axis=1)
@@ -271,9 +314,10 @@ def main(argv=None):
                 frames = dec.decode(d_rx, keys_rx, shape_rx, generator=gen)[..., :gt.shape[-2], :gt.shape[-1]]
                 check_numerics(frames, f"videos {chunk[0]}..{chunk[-1]} q{q}", recovery_note(dec))
                 x_all = frames.cpu().numpy()
+                fvds = job_fvds([(vid, x_all[j], gt[j].numpy()) for j, vid in enumerate(chunk)])
                 for j, vid in enumerate(chunk):
                     bits = [count_bits([[[[p[j]] for p in sl] for sl in k[0]], [k[1][j]]]) for k in keys]
-                    report(vid, q, 0.0, x_all[j], gt[j].numpy(), bits, mask, store)
+                    report(vid, q, 0.0, x_all[j], gt[j].numpy(), bits, mask, store, fvds[j])
     else:
         # city_sender.py:495-607 batched (policy.py): every (video, q, threshold) job of this rank advances in lockstep,
         # `--policy-batch` jobs per score-network launch; key frames coded once per (video, q, frame).
@@ -289,7 +333,9 @@ def main(argv=None):
             for q in args.q:
                 for r in res[(vid, q)]:
                     check_numerics(r["x"], f"video {vid} q{q} thr {r['thr']:.2f}", recovery_note(dec))
-                    report(vid, q, r["thr"], r["x"], clips[vid].numpy(), r["bits"], r["d"], store)
+                fvds = job_fvds([(vid, r["x"], clips[vid].numpy()) for r in res[(vid, q)]]) if res[(vid, q)] else []
+                for r, fvd in zip(res[(vid, q)], fvds):
+                    report(vid, q, r["thr"], r["x"], clips[vid].numpy(), r["bits"], r["d"], store, fvd)
                     if args.policy == "lpips":      # per-frame distances of the decoded clip (city_sender.py:570-571)
                         v = metric.values(torch.from_numpy(r["x"]).to(device), clips[vid].to(device))
                         metric_vals.setdefault(vid, []).append(v)
@@ -307,6 +353,9 @@ def main(argv=None):
         np.save(os.path.join(out_root, f"psnr_{vid}.npy"), rd_envelope(bpps, np.mean(np.asarray(ps), 1), True))
         np.save(os.path.join(out_root, f"psnr_frames_{vid}.npy"), np.asarray(ps))
         np.save(os.path.join(out_root, f"bpp_{vid}.npy"), np.asarray(bpps))
+        if vid in fvd_store:     # reference name fvd_<idx>.npy: RD envelope [bpp; FVD], lower is better; raw values beside it
+            np.save(os.path.join(out_root, f"fvd_{vid}.npy"), rd_envelope(bpps, np.asarray(fvd_store[vid]), False))
+            np.save(os.path.join(out_root, f"fvd_values_{vid}.npy"), np.asarray(fvd_store[vid]))
     D.barrier()
     if rank == 0:
         print(f"done in {time.time() - t_start:.1f}s")

@@ -80,6 +80,9 @@ HIP_SYMBOLS = {
     "evc_im2col_nchw_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p, c_void_p]),
     "evc_maxpool3s2_nhwc_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "evc_lpips_layer_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "evc_i3d_stem_im2col_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 17 + [c_void_p]),
+    "evc_maxpool3d_same_nthwc_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 11 + [c_void_p]),
+    "evc_i3d_head_f32": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
     "evc_upfirdn2d_f32": (c_int, [c_void_p, c_void_p, POINTER(c_float)] + [c_int] * 13 + [c_void_p]),
     "evc_upfirdn2d_nhwc_f32": (c_int, [c_void_p, c_void_p, POINTER(c_float)] + [c_int] * 10 +
                                [c_void_p, c_void_p, c_int, c_void_p]),
@@ -407,6 +410,46 @@ def lpips_layer(f0, f1, lin_w, dist, accumulate):
     _check(hip_lib().evc_lpips_layer_f32(fptr(f0), fptr(f1), fptr(lin_w), fptr(dist), N, H * W, C, int(bool(accumulate)),
                                          stream_ptr()), "evc_lpips_layer_f32")
     return dist
+
+
+def same_pad(size, k, s):
+    """TensorFlow "same" padding of I3D (include/evc_hip.h): (front, back)."""
+    p = max(k - s, 0) if size % s == 0 else max(k - size % s, 0)
+    return p // 2, p - p // 2
+
+
+def i3d_stem_im2col(x, Hr, Wr, R, k, s, f_begin, out):
+    """x: (B, T, C, H, W) clips in [0, 1] -> ``out`` (nf, Ho, Wo, ld_out): rows of output frames f_begin .. f_begin + nf - 1 of
+    the k^3 stride-s first I3D convolution over the resized (Hr x Wr), centre-cropped (R x R), [-1, 1]-scaled, same-padded clip."""
+    B, T, C, H, W = x.shape
+    nf, Ho, Wo, ld = out.shape
+    To = (T + sum(same_pad(T, k, s)) - k) // s + 1
+    assert (Ho, Wo) == ((R + sum(same_pad(R, k, s)) - k) // s + 1,) * 2 and f_begin + nf <= B * To
+    _check(hip_lib().evc_i3d_stem_im2col_f32(fptr(x), fptr(out), B, T, C, H, W, Hr, Wr, R, k, k, k, s, s, s, f_begin, nf, ld,
+                                             stream_ptr()), "evc_i3d_stem_im2col_f32")
+    return out
+
+
+def maxpool3d_same_nthwc(x, T, kernel, stride):
+    """MaxPool3dSamePadding on (B*T, H, W, C) NTHWC activations -> (B*To, Ho, Wo, C); zero padding, as the reference pads."""
+    BT, H, W, C = x.shape
+    assert BT % T == 0
+    B = BT // T
+    To, Ho, Wo = ((n + sum(same_pad(n, k, s)) - k) // s + 1 for n, k, s in zip((T, H, W), kernel, stride))
+    out = torch.empty((B * To, Ho, Wo, C), device=x.device, dtype=torch.float32)
+    _check(hip_lib().evc_maxpool3d_same_nthwc_f32(fptr(x), fptr(out), B, T, H, W, C, *kernel, *stride, stream_ptr()),
+           "evc_maxpool3d_same_nthwc_f32")
+    return out
+
+
+def i3d_head(x, T, w, bias, kt):
+    """x: (B*T, H, W, C) -> (B, Co): AvgPool3d((kt, H, W), stride 1), 1x1x1 logits unit w (Co, C) + bias, mean over windows."""
+    BT, H, W, C = x.shape
+    assert BT % T == 0 and w.shape[1] == C
+    out = torch.empty((BT // T, w.shape[0]), device=x.device, dtype=torch.float32)
+    _check(hip_lib().evc_i3d_head_f32(fptr(x), fptr(w), fptr(bias), fptr(out), BT // T, T, H * W, C, w.shape[0], kt,
+                                      stream_ptr()), "evc_i3d_head_f32")
+    return out
 
 
 class ClockProbe:

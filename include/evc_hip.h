@@ -381,6 +381,36 @@ int evc_maxpool3s2_nhwc_f32(const float* x, float* out, int N, int H, int W, int
 int evc_lpips_layer_f32(const float* f0, const float* f1, const float* lin_w, float* dist, int N, int HW, int C, int accumulate,
                         void* stream);
 
+/* ---- I3D (InceptionI3d(400), the feature network of the Frechet video distance) ----------------------------------
+ * Replaces the detector of calculate_fvd (city_sender.py:264-279, called per job at :575-589): preprocess_single
+ * (models/fvd/fvd.py: bilinear resize, align_corners=False, of the shorter side to R = 224, the other side ceil-ed, centre
+ * crop R x R, (x - 0.5) * 2) and InceptionI3d.forward (models/fvd/pytorch_i3d.py:316-327) with TensorFlow-"same" zero padding
+ * everywhere (compute_pad, :9-34 and :71-99: pad = max(k - s, 0) when s divides the size, else max(k - size % s, 0); the
+ * front gets pad / 2, the back the rest).  Activations are NTHWC: B*T images of H x W x C.  The 1x1x1 units and the 3x3x3
+ * units (after evc_frame_taps_f32) run on evc_conv2d_nhwc_f32 with BatchNorm folded into weight and bias; these are the other
+ * pieces (csrc/i3d.hip):
+ *   evc_i3d_stem_im2col_f32   clips x (B, T, C, H, W) in [0, 1] -> out (nf, Ho, Wo, ld_out): the rows of output frames
+ *                         f_begin .. f_begin + nf - 1 (flattened f = b*To + t) of the KT x KH x KW stride-(ST, SH, SW) first
+ *                         convolution (Conv3d_1a_7x7, pytorch_i3d.py:209-211) over the preprocessed clip, in (c, kt, ky, kx)
+ *                         order, columns C*KT*KH*KW .. ld_out-1 zero.  The resize to Hr x Wr, the crop at ((Hr - R) / 2,
+ *                         (Wr - R) / 2), the scaling and the same padding of the R x R crop are applied while sampling; the
+ *                         resized video is never written.  To = ceil(T / ST), Ho = ceil(R / SH), Wo = ceil(R / SW); the
+ *                         caller's `out` holds nf * Ho * Wo * ld_out floats (that is the workspace bound: chunk nf to fit it).
+ *                         The convolution is then a 1x1 one over ld_out channels.
+ *   evc_maxpool3d_same_nthwc_f32   MaxPool3dSamePadding (pytorch_i3d.py:7-34): window KT x KH x KW, strides ST, SH, SW,
+ *                         zero padding (the padding takes part in the max) -> (B, ceil(T/ST), ceil(H/SH), ceil(W/SW), C),
+ *                         C % 4 == 0.  Exactly F.max_pool3d(F.pad(x, same)).
+ *   evc_i3d_head_f32      the logits of pytorch_i3d.py:322-327: AvgPool3d((KT, H, W), stride 1) over x (B, T, H*W, C) -- the
+ *                         window covers the whole H x W frame -- the 1x1x1 logits unit (w: (Co, C) row-major, bias: (Co,) or
+ *                         NULL) and the mean over the T - KT + 1 windows, as one linear map: frame t is weighted by the number
+ *                         of windows holding it over KT * HW * (T - KT + 1).  out: (B, Co).  C <= 2048, T >= KT. */
+int evc_i3d_stem_im2col_f32(const float* x, float* out, int B, int T, int C, int H, int W, int Hr, int Wr, int R, int KT, int KH,
+                            int KW, int ST, int SH, int SW, int f_begin, int nf, int ld_out, void* stream);
+int evc_maxpool3d_same_nthwc_f32(const float* x, float* out, int B, int T, int H, int W, int C, int KT, int KH, int KW, int ST,
+                                 int SH, int SW, void* stream);
+int evc_i3d_head_f32(const float* x, const float* w, const float* bias, float* out, int B, int T, int HW, int C, int Co, int KT,
+                     void* stream);
+
 /* ---- GDN (not on the decode path: g_s / g_a contain none) ---------------------------------
  * y = x * rsqrt(beta + gamma . x^2) (inverse: * sqrt) -- GDN.forward, ELICUtilis/layers/gdn.py:62-77; simplified != 0:
  * y = x / (beta + gamma . |x|) -- GDN1.forward, :95-106.  x, out: NHWC with C % 16 == 0; gamma_packed = the
