@@ -107,7 +107,7 @@ __device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_r
 
 __device__ __forceinline__ float act_fn(float v, int act) {
     if (act == EVC_ACT_SILU) return silu_f(v);
-    if (act == EVC_ACT_RELU) return fmaxf(v, 0.0f);
+    if (act == EVC_ACT_RELU) return v < 0.f ? 0.f : v;   // NaN passes, as torch.relu
     return v;
 }
 
@@ -120,7 +120,7 @@ __device__ __forceinline__ float4 transform(float4 v, const float4& a, const flo
         v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w);
     }
     if (MODE == MODE_RELU) {
-        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+        v.x = v.x < 0.f ? 0.f : v.x; v.y = v.y < 0.f ? 0.f : v.y; v.z = v.z < 0.f ? 0.f : v.z; v.w = v.w < 0.f ? 0.f : v.w;
     }
     v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
     return v;

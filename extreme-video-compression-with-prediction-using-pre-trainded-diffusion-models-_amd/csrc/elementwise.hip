@@ -11,6 +11,9 @@ inline int grid_for(size_t n, int cap = 4096) {
 }
 #define EVC_LAUNCH_OK() (hipGetLastError() == hipSuccess ? EVC_OK : EVC_ELAUNCH)
 
+// torch.clamp: a NaN passes through (fminf / fmaxf would return the bound instead), +-inf clamps like any other value.
+__device__ __forceinline__ float clamp_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
 // out[b][h][w][c] = c < C0 ? x0[b][c][h][w] : c < C0+C1 ? x1[b][c-C0][h][w] : 0.
 // One thread = one pixel, all of its Cpad channels: every plane is read coalesced along w (lanes walk pixels) and the
 // pixel's row is written as float4s, so a wave writes 64 * Cpad * 4 contiguous bytes (round 1 wrote one float per lane
@@ -55,7 +58,7 @@ __global__ void ddpm_step_kernel(float* __restrict__ x, const float* __restrict_
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float xv = x[i];
         float x0 = k1 * (xv - k2 * e[i]);
-        if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+        if (clip) x0 = clamp_nan(x0, -1.f, 1.f);
         float y = c1 * x0 + c2 * xv;
         if (noise) y += sigma * noise[i];
         x[i] = y;
@@ -67,7 +70,7 @@ __global__ void ddim_step_kernel(float* __restrict__ x, const float* __restrict_
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float ev = e[i];
         float x0 = k1 * (x[i] - k2 * ev);
-        if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+        if (clip) x0 = clamp_nan(x0, -1.f, 1.f);
         x[i] = c1 * x0 + c2 * ev;
     }
 }
@@ -83,7 +86,7 @@ __global__ void pndm_transfer_kernel(const float* __restrict__ x, const float* _
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float xv = x[i];
         float v = xv + d * (cx * xv - ce * e[i]);
-        if (clip) v = fminf(fmaxf(v, -1.f), 1.f);
+        if (clip) v = clamp_nan(v, -1.f, 1.f);
         y[i] = v;
     }
 }
@@ -104,7 +107,7 @@ __global__ void scale_clamp_kernel(const float* __restrict__ x, float* __restric
                                    int clamp, float lo, float hi) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         float v = x[i] * mul + add;
-        if (clamp) v = fminf(fmaxf(v, lo), hi);
+        if (clamp) v = clamp_nan(v, lo, hi);
         y[i] = v;
     }
 }

@@ -20,7 +20,7 @@ struct FirGeom {
 
 __device__ __forceinline__ float act_fn(float v, int act) {
     if (act == EVC_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-    if (act == EVC_ACT_RELU) return fmaxf(v, 0.0f);
+    if (act == EVC_ACT_RELU) return v < 0.f ? 0.f : v;   // NaN passes, as torch.relu
     return v;
 }
 

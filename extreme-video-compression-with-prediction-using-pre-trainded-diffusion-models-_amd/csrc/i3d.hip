@@ -14,6 +14,9 @@
 
 namespace {
 
+// Running max that keeps a NaN, as torch's max_pool does (fmaxf returns the operand that is not NaN).
+__device__ __forceinline__ float max_nan(float m, float v) { return (v > m || v != v) ? v : m; }
+
 // PyTorch's bilinear source index, align_corners=False, output size given (area_pixel_compute_source_index).
 struct Lin { int i0, i1; float l0, l1; };
 __device__ inline Lin lin_src(int dst, float scale, int in) {
@@ -79,7 +82,7 @@ __global__ void maxpool3d_same_kernel(const float4* __restrict__ x, float4* __re
                     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
                     if (t >= 0 && t < T && y >= 0 && y < H && xx >= 0 && xx < W)
                         v = x[(((b * T + t) * H + y) * W + xx) * C4 + c];
-                    m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+                    m.x = max_nan(m.x, v.x); m.y = max_nan(m.y, v.y); m.z = max_nan(m.z, v.z); m.w = max_nan(m.w, v.w);
                 }
             }
         }

@@ -19,6 +19,9 @@
 
 namespace {
 
+// Running max that keeps a NaN, as torch's max_pool does (fmaxf returns the operand that is not NaN).
+__device__ __forceinline__ float max_nan(float m, float v) { return (v > m || v != v) ? v : m; }
+
 // out[n][oy][ox][(c*KH + ky)*KW + kx] = in-range ? (x[n][c][oy*s - pad + ky][ox*s - pad + kx] - shift[c]) / scale[c] : 0;
 // channels K = C*KH*KW .. ld_out-1 are zero.  One thread per output element (coalesced writes along the patch axis).
 __global__ void im2col_kernel(const float* __restrict__ x, float* __restrict__ out, int C, int H, int W, int KH, int KW,
@@ -59,7 +62,7 @@ __global__ void maxpool3s2_kernel(const float4* __restrict__ x, float4* __restri
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
                 const float4 v = x[((n * H + (2 * oy + ky)) * W + (2 * ox + kx)) * C4 + c];
-                m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+                m.x = max_nan(m.x, v.x); m.y = max_nan(m.y, v.y); m.z = max_nan(m.z, v.z); m.w = max_nan(m.w, v.w);
             }
         out[i] = m;
     }

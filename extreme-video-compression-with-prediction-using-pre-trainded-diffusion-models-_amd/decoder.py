@@ -78,7 +78,7 @@ class ClipDecoder:
 
         def run():
             res["frames"], res["raw"] = self._generate(cond_frames, noise_fn, generator, groups, with_raw=True)
-            return res["raw"]          # the sampler's output before the clamp of inverse_data_transform (clamping hides NaN)
+            return res["raw"]          # the sampler's output before inverse_data_transform (its clamp keeps NaN, but turns an inf into 0 / 1)
 
         _, passes, new = generate_with_recovery(run, restore, net, where=f"chunk {self.chunks}", log=self.log)
         if new:

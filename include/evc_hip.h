@@ -98,9 +98,11 @@ int evc_gn_coeffs_f32(const float* part0, int nsplit0, int C0, const float* part
 
 /* Range events of the fp16-split arithmetic (EVC_ARITH_F16X3).  That arithmetic scales its operands by powers of two
  * into fp16's range WITHOUT clamping: an operand element beyond the range becomes inf in the split and NaN in the output
- * (loud, never a silently saturated number), and a NaN / inf input stays non-finite.  Whether that can happen is decided
- * on O(B*C) numbers by the kernels that see every tensor's moments -- the two functions below -- which OR these bits into
- * the caller's sticky device word `events` (may be NULL; never cleared by a kernel):
+ * (loud, never a silently saturated number), and a NaN / inf input stays non-finite.  That last promise covers every
+ * export of this header, not only the fp16-split path: clamps, ReLUs and max pools pass a NaN through, as torch does.
+ * Whether an operand can leave fp16's range is decided on O(B*C) numbers by the kernels that see every tensor's moments
+ * -- the two functions below -- which OR these bits into the caller's sticky device word `events` (may be NULL; never
+ * cleared by a kernel):
  *   EVC_RANGE_NONFINITE    a tensor's moments are not finite: it holds a NaN or an infinity;
  *   EVC_RANGE_F16_OPERAND  for some channel |coef_a| * max|x| + |coef_s| >= 65504 / 8: a GroupNorm-ed (and activated,
  *                          |SiLU(v)| <= |v|) operand element MAY leave fp16's range.  Zero means none can (a sufficient
