@@ -12,7 +12,9 @@ the explicit fallback ``mask`` (fixed transmit mask) runs and the CLI says so; `
 ``decide_5to5`` (city_sender.py:353-374); ``--synthetic`` builds seeded stand-ins when checkpoints / data are
 absent.  ``--fvd`` (or ``i3d_pretrained_400.pt`` found where the reference keeps it, ``find_i3d_weights``) adds the
 reference's third per-job number, the FVD of the decoded clip against the original (city_sender.py:575-589), computed by the
-HIP I3D network (fvd.py) and saved as ``fvd_<idx>.npy``.  ``--gpus N`` (or ``torch.distributed.run``) block-shards the video range over N ranks, one GPU each.
+HIP I3D network (fvd.py) and saved as ``fvd_<idx>.npy``.  Under a decision rule ``--bitstream-dir DIR`` writes one replayable
+job stream per reported job (container format 3) for ``city_receiver.py`` and runs the sweep on noise specification N1
+(``--noise evc``).  ``--gpus N`` (or ``torch.distributed.run``) block-shards the video range over N ranks, one GPU each.
 """
 import argparse
 import os
@@ -77,7 +79,13 @@ def build_parser():
     p.add_argument("--groups", type=int, default=1, help="concurrent clip groups (HIP streams) inside a batch")
     p.add_argument("--bitstream-dir", type=str, default=None,
                    help="mask policy: write each batch's key-frame strings + mask as an EVC1 container here and "
-                        "decode from the bytes read back (container.py)")
+                        "decode from the bytes read back (container.py); psnr / lpips policy: write one job stream "
+                        "job_v<vid>_q<q>_thr<thr>.evc per reported job (container format 3) for city_receiver.py -- the "
+                        "sweep then runs on the replayable noise (--noise evc)")
+    p.add_argument("--noise", choices=["torch", "evc"], default=None,
+                   help="psnr / lpips policy: torch (default) = one seeded torch.Generator per (job, round, step); evc = noise "
+                        "specification N1 drawn by one HIP launch per step (DESIGN.md section 5), the only noise a receiver "
+                        "can replay: --bitstream-dir selects it")
     p.add_argument("--range-recovery", choices=["off", "layer"], default=None,
                    help="layer: when a chunk raises an fp16-split range event, demote only the layers that raised it to the "
                         "bf16x6 split and regenerate the chunk with the same noise (default: EVC_RANGE_RECOVERY, else off: "
@@ -191,6 +199,14 @@ def main(argv=None):
     from .scorenet import build_score_network
 
     resolve_policy(args, log=lambda m: print(m, flush=True))
+    if args.policy != "mask":
+        if args.bitstream_dir and args.noise == "torch":
+            sys.exit("--bitstream-dir with --noise torch: a job stream whose frames depend on torch's generators cannot be "
+                     "replayed by a receiver; drop --noise or pass --noise evc")
+        if args.bitstream_dir and args.noise is None:
+            print("noise: evc (specification N1) because --bitstream-dir writes job streams a receiver must replay", flush=True)
+            args.noise = "evc"
+        args.noise = args.noise or "torch"
     fvd_path = resolve_fvd(args, log=lambda m: print(m, flush=True))
     cfg, raw = C.load_config(args.config, args.config_mod)
     if args.subsample is not None:
@@ -327,7 +343,12 @@ def main(argv=None):
                           log=lambda m: print(f"[rank {rank}] {m}", flush=True))
         clips = {vid: torch.from_numpy(np.asarray(data[vid], dtype=np.float32) / 255.0) for vid in vids}
         res = P.run_policy(dec, models, clips, args.q, thresholds, metric, patch=args.patch, max_batch=args.policy_batch,
-                           seed=args.seed, device=device, bpp_limit=args.bpp_limit, log=lambda m: print(f"[rank {rank}] {m}", flush=True))
+                           seed=args.seed, device=device, bpp_limit=args.bpp_limit, log=lambda m: print(f"[rank {rank}] {m}", flush=True),
+                           noise=args.noise)
+        if args.bitstream_dir:       # one replayable stream per reported job (receiver.py decodes them)
+            from .receiver import write_job_streams
+            written = write_job_streams(args.bitstream_dir, res, models, args.sampler, cfg)
+            print(f"[rank {rank}] wrote {len(written)} job stream(s) to {args.bitstream_dir}", flush=True)
         metric_vals = {}
         for vid in vids:
             for q in args.q:

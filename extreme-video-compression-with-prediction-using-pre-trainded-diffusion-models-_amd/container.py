@@ -15,6 +15,9 @@ summation order changes).  A learned codec's range decoder desynchronises if a p
 a receiver whose networks run another arithmetic must REFUSE the stream (``CodecMismatch``) rather than decode garbage.
 
 The payload bytes are exactly the strings the codec produced, so ``8 * payload`` equals the reference's bit count.
+
+Format 3 (``pack_job`` / ``unpack_job``, further down) is the stream of ONE policy job: its program of key / generated
+segments and the key of its noise, so that a receiver replays exactly what the sender judged.
 """
 import struct
 
@@ -100,6 +103,137 @@ def unpack(blob, expect_codec=None):
     if off != len(blob):
         raise ValueError("trailing bytes in container")
     return d, key_strings, (sh, sw)
+
+
+# ---- format 3: one policy job ----------------------------------------------------------------------------------
+# A policy job (policy.run_policy: one (video, q, threshold)) has its own mask, and the mask alone does not describe it:
+# the sender cuts a run of generated frames where its metric stopped accepting, and every generation round draws the noise
+# of its own key.  The job stream therefore carries the job's PROGRAM -- the segment list -- and what names its noise:
+#
+#     magic "EVC1" | u8 format (3) | u8 arith | u16 codec_rev
+#                  | u8 noise spec (1 = N1) | u64 seed | u32 stream id
+#                  | u32 video index | u8 q | f32 threshold                      (the job's identity)
+#                  | u8 sampler id | u16 subsample steps | u8 denoise            (what the generator needs beyond the checkpoint)
+#                  | u16 frames | u16 shape_h | u16 shape_w | u16 n_key | u16 n_segments
+#                  | n_segments x (u8 kind: 0 = key, 1 = gen | u8 n)
+#     then for every key frame in order:  u32 len(z) | z | for slice 0..4, pass 0..1:  u32 len | bytes
+#
+# ("key", n): n key frames decoded in one ELIC call; ("gen", n): one generation round from the last two decoded frames of
+# which the first n frames are kept, its noise keyed by (seed, stream id, start frame = frames decoded so far, step).
+FORMAT_JOB = 3
+NOISE_N1 = 1
+NOISE_SPECS = {NOISE_N1: "N1"}
+SAMPLER_IDS = {"DDPM": 0, "DDIM": 1, "FPNDM": 2}
+SAMPLER_NAMES = {v: k for k, v in SAMPLER_IDS.items()}
+SEGMENT_KINDS = ("key", "gen")
+CHUNK = 5                          # frames of one generation round
+_JOB_HEAD = "<BQIIBfBHBHHHHH"      # noise spec ... n_segments
+
+
+def check_segments(segments, frames, n_key=None):
+    """The consistency rules of a job's program; raises ValueError.  -> the transmit mask d."""
+    d, t = [], 0
+    for kind, n in segments:
+        if kind not in SEGMENT_KINDS:
+            raise ValueError(f"corrupt job stream: unknown segment kind {kind!r}")
+        if kind == "key":
+            if n < 1:
+                raise ValueError("corrupt job stream: empty key segment")
+        else:
+            if not 1 <= n <= CHUNK:
+                raise ValueError(f"corrupt job stream: a generation round keeps 1..{CHUNK} frames, not {n}")
+            if t < 2:
+                raise ValueError("corrupt job stream: a generated segment needs two decoded frames before it")
+        d += [1 if kind == "key" else 0] * n
+        t += n
+    if t != frames:
+        raise ValueError(f"corrupt job stream: segments add up to {t} frames, header says {frames}")
+    if n_key is not None and sum(d) != n_key:
+        raise ValueError(f"corrupt job stream: segments name {sum(d)} key frames, the stream holds {n_key}")
+    return np.asarray(d, dtype=np.int64)
+
+
+def pack_job(segments, key_strings, shape, codec, seed, stream_id, vid, q, thr, sampler, subsample, denoise,
+             noise_spec=NOISE_N1):
+    """One policy job -> bytes.  segments: [("key" | "gen", n)]; key_strings: per key frame, in order, ``[y_strings[5][2][1],
+    z_strings[1]]`` (one clip); codec: ``ElicModel.codec_tag()`` of the encoder; sampler: "DDPM" | "DDIM" | "FPNDM"."""
+    segments = [(str(k), int(n)) for k, n in segments]
+    frames = sum(n for _, n in segments)
+    check_segments(segments, frames, len(key_strings))
+    out = [MAGIC, struct.pack("<BBH", FORMAT_JOB, int(codec[0]), int(codec[1])),
+           struct.pack(_JOB_HEAD, int(noise_spec), int(seed) & (2 ** 64 - 1), int(stream_id), int(vid), int(q), float(thr),
+                       SAMPLER_IDS[sampler], int(subsample), int(bool(denoise)), frames, int(shape[0]), int(shape[1]),
+                       len(key_strings), len(segments))]
+    out += [struct.pack("<BB", SEGMENT_KINDS.index(k), n) for k, n in segments]
+    for ys, zs in key_strings:
+        assert len(zs) == 1, "a job stream holds one clip"
+        out.append(struct.pack("<I", len(zs[0])) + zs[0])
+        for i in range(N_SLICES):
+            for p in range(N_PASSES):
+                out.append(struct.pack("<I", len(ys[i][p][0])) + ys[i][p][0])
+    return b"".join(out)
+
+
+def unpack_job(blob, expect_codec=None):
+    """bytes of ``pack_job`` -> dict(codec, noise_spec, seed, stream_id, vid, q, thr, sampler, subsample, denoise, frames,
+    shape, segments, d, key_strings).  Raises ValueError for anything but a complete, consistent format-3 stream of a known
+    noise specification, ``CodecMismatch`` for a stream coded under another arithmetic / kernel revision."""
+    if blob[:4] != MAGIC or len(blob) < 8:
+        raise ValueError("not an EVC1 container")
+    fmt, arith, rev = struct.unpack_from("<BBH", blob, 4)
+    if fmt != FORMAT_JOB:
+        raise ValueError(f"not a job stream: EVC1 container format {fmt} (job streams are format {FORMAT_JOB})")
+    if expect_codec is not None and (arith, rev) != tuple(int(v) for v in expect_codec):
+        raise CodecMismatch(f"stream was coded with convolution arithmetic {ARITH_NAMES.get(arith, arith)} rev {rev}, this "
+                            f"receiver runs {ARITH_NAMES.get(int(expect_codec[0]), expect_codec[0])} rev {int(expect_codec[1])}: "
+                            "the entropy parameters would differ in the last bit and the range decoder would desynchronise")
+    off = 8
+    if off + struct.calcsize(_JOB_HEAD) > len(blob):
+        raise ValueError("truncated job stream")
+    (spec, seed, stream_id, vid, q, thr, sampler, subsample, denoise, frames, sh, sw, n_key,
+     n_seg) = struct.unpack_from(_JOB_HEAD, blob, off)
+    off += struct.calcsize(_JOB_HEAD)
+    if spec not in NOISE_SPECS:
+        raise ValueError(f"unknown noise specification id {spec} (this build replays {sorted(NOISE_SPECS)} = "
+                         f"{', '.join(NOISE_SPECS.values())})")
+    if sampler not in SAMPLER_NAMES:
+        raise ValueError(f"corrupt job stream: unknown sampler id {sampler}")
+    if off + 2 * n_seg > len(blob):
+        raise ValueError("truncated job stream")
+    segments = []
+    for s in range(n_seg):
+        kind, n = struct.unpack_from("<BB", blob, off + 2 * s)
+        if kind >= len(SEGMENT_KINDS):
+            raise ValueError(f"corrupt job stream: unknown segment kind {kind}")
+        segments.append((SEGMENT_KINDS[kind], n))
+    off += 2 * n_seg
+    d = check_segments(segments, frames, n_key)
+
+    def take():
+        nonlocal off
+        if off + 4 > len(blob):
+            raise ValueError("truncated job stream")
+        (n,) = struct.unpack_from("<I", blob, off)
+        off += 4
+        if off + n > len(blob):
+            raise ValueError("truncated job stream")
+        s = bytes(blob[off:off + n])
+        off += n
+        return s
+    key_strings = []
+    for _ in range(n_key):
+        zs = [take()]
+        ys = [[[take()] for _ in range(N_PASSES)] for _ in range(N_SLICES)]
+        key_strings.append([ys, zs])
+    if off != len(blob):
+        raise ValueError("trailing bytes in job stream")
+    return dict(codec=(arith, rev), noise_spec=spec, seed=seed, stream_id=stream_id, vid=vid, q=q, thr=thr,
+                sampler=SAMPLER_NAMES[sampler], subsample=subsample, denoise=bool(denoise), frames=frames, shape=(sh, sw),
+                segments=segments, d=d, key_strings=key_strings)
+
+
+def job_file_name(vid, q, thr):
+    return "job_v%d_q%d_thr%.2f.evc" % (vid, q, thr)
 
 
 def payload_bits(key_strings):

@@ -184,6 +184,75 @@ class ClipDecoder:
                 t += run
         return torch.cat(out, dim=1)[:, :frames].contiguous()
 
+    @torch.no_grad()
+    def decode_jobs(self, jobs, max_batch=32, models=None, size=None):
+        """Decode policy-job streams (``container.unpack_job`` dicts; possibly different q, masks and program lengths).
+
+        All jobs advance in lockstep, as ``policy.run_policy`` advances them on the sender: each round every unfinished job
+        executes its next segment.  The jobs whose segment is ("gen", n) are stacked along the batch axis of one
+        ``generate`` call (``max_batch`` per launch), each drawing the noise of its own key (seed, stream id, start frame =
+        frames it holds so far, step) -- noise specification N1 -- and keep the first n frames; the jobs whose segment is
+        ("key", n) decode its n frames in one ``decompress`` call per q (several jobs share a call up to ``max_batch``
+        frames; a segment is never split).  ``models``: q -> ElicModel (default: this decoder's own model for every q);
+        ``size`` = (H, W) of a frame (default: the generator's image size): the ELIC output is cropped to it, as the sender
+        crops its padded frames.  The generator settings of the streams (sampler, subsample steps, denoise) must be the ones
+        this decoder was built with.  Returns one (frames, 3, H, W) float32 device tensor per job."""
+        from . import container as Cn, sampler as S
+        cfg = self.config
+        mine = (getattr(cfg.sampling, "subsample", None) or 0, bool(cfg.sampling.denoise))
+        for job in jobs:
+            if job["noise_spec"] != Cn.NOISE_N1:
+                raise ValueError(f"unknown noise specification id {job['noise_spec']}")
+            if S.get_sampler(job["sampler"]) is not self.sampler or (job["subsample"], job["denoise"]) != mine:
+                raise ValueError(f"job stream v{job['vid']} q{job['q']} thr {job['thr']:.2f} was generated with "
+                                 f"{job['sampler']}-{job['subsample']} denoise={job['denoise']}: build the decoder with them")
+            Cn.check_segments(job["segments"], job["frames"], len(job["key_strings"]))
+        H, W = size if size is not None else (cfg.data.image_size, cfg.data.image_size)
+        model_of = (lambda q: self.elic) if models is None else (lambda q: models[q])
+        ch = cfg.data.channels * cfg.data.num_frames
+        x = [[] for _ in jobs]             # decoded frames per job
+        pos = [0] * len(jobs)              # next segment
+        used = [0] * len(jobs)             # key frames consumed
+        while True:
+            todo = [i for i, job in enumerate(jobs) if pos[i] < len(job["segments"])]
+            if not todo:
+                break
+            gen = [i for i in todo if jobs[i]["segments"][pos[i]][0] == "gen"]
+            key = [i for i in todo if jobs[i]["segments"][pos[i]][0] == "key"]
+            for seed in sorted({jobs[i]["seed"] for i in gen}):          # one seed per noise launch
+                same = [i for i in gen if jobs[i]["seed"] == seed]
+                for c0 in range(0, len(same), max_batch):
+                    part = same[c0:c0 + max_batch]
+                    cond = torch.stack([torch.stack(x[i][-2:], 0) for i in part], 0).contiguous()
+                    keys = L.noise_keys([(jobs[i]["stream_id"], len(x[i])) for i in part], self.device)
+                    pred = self.generate(cond, groups=1, noise_fn=lambda tag, shape, keys=keys, seed=seed: L.noise_normal(
+                        keys, shape, seed, 0 if tag == "init" else int(tag) + 1))
+                    assert pred.shape[1] * pred.shape[2] == ch
+                    for k, i in enumerate(part):
+                        x[i] += [pred[k, t] for t in range(jobs[i]["segments"][pos[i]][1])]
+            for q in sorted({jobs[i]["q"] for i in key}):
+                same = [i for i in key if jobs[i]["q"] == q]
+                while same:
+                    part, n = [], 0
+                    while same and (not part or n + jobs[same[0]]["segments"][pos[same[0]]][1] <= max_batch):
+                        n += jobs[same[0]]["segments"][pos[same[0]]][1]
+                        part.append(same.pop(0))
+                    shape = jobs[part[0]]["shape"]
+                    assert all(tuple(jobs[i]["shape"]) == tuple(shape) for i in part), "one frame size per decoder"
+                    ks = [jobs[i]["key_strings"][used[i] + f] for i in part for f in range(jobs[i]["segments"][pos[i]][1])]
+                    ys = [[[s for k_ in ks for s in k_[0][sl][p]] for p in range(2)] for sl in range(len(ks[0][0]))]
+                    zs = [s for k_ in ks for s in k_[1]]
+                    x_hat = model_of(q).decompress([ys, zs], shape)["x_hat"][:, :, :H, :W]
+                    o = 0
+                    for i in part:
+                        n_i = jobs[i]["segments"][pos[i]][1]
+                        x[i] += [x_hat[o + f] for f in range(n_i)]
+                        o += n_i
+                        used[i] += n_i
+            for i in todo:
+                pos[i] += 1
+        return [torch.stack(f, 0).contiguous() for f in x]
+
 
 def total_bits(key_strings):
     return sum(count_bits(s) for s in key_strings)

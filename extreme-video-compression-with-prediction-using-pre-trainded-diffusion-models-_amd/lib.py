@@ -6,7 +6,7 @@ device raises ``EvcLibraryError`` so a silent eager/CPU substitute can never pas
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_longlong, c_uint8, c_void_p
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_longlong, c_uint, c_uint8, c_ulonglong, c_void_p
 
 import numpy as np
 import torch
@@ -158,6 +158,7 @@ HIP_SYMBOLS = {
                                                                        c_void_p]),
     "evc_elic_scatter_symbols_f32": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     "evc_elic_quantize_f32": (c_int, [c_void_p, c_int, c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p]),
+    "evc_noise_normal_f32": (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_ulonglong, c_uint, c_int, c_void_p]),
 }
 
 RANS_SYMBOLS = {
@@ -953,6 +954,27 @@ def scale_clamp(x, mul, add, clamp=None, out=None):
     _check(hip_lib().evc_scale_clamp_f32(fptr(x), fptr(out), x.numel(), mul, add, int(clamp is not None), lo, hi,
                                          stream_ptr()), "evc_scale_clamp_f32")
     return out
+
+
+def noise_keys(pairs, device):
+    """[(stream id, start frame)] -> the device key array [B][2] of ``noise_normal`` (uint32 bits in an int32 tensor)."""
+    k = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    assert k.size and k.min() >= 0 and k.max() < 2 ** 32, "stream ids and start frames are u32"
+    return torch.from_numpy(k.astype(np.uint32).view(np.int32)).to(device).contiguous()
+
+
+def noise_normal(keys, shape, seed, step, raw=False, out=None):
+    """Noise specification N1 (include/evc_hip.h evc_noise_normal_f32): standard normals (``raw``: the Philox words, int32) of
+    sampler step tag ``step`` for a batch, sample b from the stream of keys[b] = (stream id, start frame).  shape: (B, ...)."""
+    B = int(shape[0])
+    n = int(np.prod(shape[1:]))
+    assert keys.dtype == torch.int32 and tuple(keys.shape) == (B, 2)
+    if out is None:
+        out = torch.empty(tuple(shape), device=keys.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.numel() == B * n
+    _check(hip_lib().evc_noise_normal_f32(fptr(out), ptr(keys), B, n, int(seed) & (2 ** 64 - 1), int(step), int(bool(raw)),
+                                          stream_ptr()), "evc_noise_normal_f32")
+    return out.view(torch.int32) if raw else out
 
 
 def gate_residual(a, b, x, out=None):

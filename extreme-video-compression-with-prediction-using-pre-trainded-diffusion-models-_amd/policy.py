@@ -10,7 +10,10 @@ the batch axis of one score-network launch (``max_batch`` per launch), and the k
 one batched ELIC call per q, once per (video, q, frame) however many thresholds fall back to it.
 
 Noise: every job draws from its own counter-based stream (seed, job id, round, step), so a job's frames do not depend
-on which other jobs share its launch -- the batched sweep and a one-job-at-a-time run make the same decisions.
+on which other jobs share its launch -- the batched sweep and a one-job-at-a-time run make the same decisions.  With
+``noise="evc"`` the stream is the project's own specification N1 (csrc/noise.hip) keyed by (seed, job id, start frame, step),
+which a receiver can derive from the job stream alone; the result then carries the job's program (``segments``) and key-frame
+strings, everything ``container.pack_job`` needs.
 
 Metrics: ``PsnrMetric`` is the reference's ``decide_5to5`` rule (accept while PSNR >= threshold, cal_psnr of
 city_sender.py:257-260).  ``CallableMetric`` is the hook for ``decide_5to5_lpips`` (accept while distance <=
@@ -19,10 +22,12 @@ by the user (``--policy lpips --metric pkg.module:function`` or the ``lpips`` pa
 """
 import importlib
 import os
+import time
 
 import numpy as np
 import torch
 
+from . import lib as L
 from .elic import count_bits
 
 
@@ -106,16 +111,30 @@ def inference_batch(model, x, patch):
     return dec, bits
 
 
+def coded_batch(model, x, patch):
+    """``inference_batch`` that also keeps what a receiver needs: -> (x_hat, bits[n], strings[n], shape), strings[b] =
+    ``[y_strings[5][2][1], z_strings[1]]`` of frame b alone (the per-key-frame entry of a job stream, container.pack_job)."""
+    n, _, h, w = x.shape
+    ph, pw = (-h) % patch, (-w) % patch
+    xp = torch.nn.functional.pad(x, (0, pw, 0, ph))
+    enc = model.compress(xp)
+    dec = model.decompress(enc["strings"], enc["shape"])["x_hat"][:, :, :h, :w]
+    ys, zs = enc["strings"]
+    strings = [[[[[p[b]] for p in sl] for sl in ys], [zs[b]]] for b in range(n)]
+    return dec, [count_bits(s) for s in strings], strings, enc["shape"]
+
+
 class _Job:
-    __slots__ = ("uid", "vid", "q", "thr", "x", "d", "bits", "round")
+    __slots__ = ("uid", "vid", "q", "thr", "x", "d", "bits", "round", "segments", "strings")
 
     def __init__(self, uid, vid, q, thr):
         self.uid, self.vid, self.q, self.thr = uid, vid, q, thr
         self.x, self.d, self.bits, self.round = [], [], [], 0
+        self.segments, self.strings = [], []
 
 
 def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=30, max_batch=32, seed=0,
-               bpp_limit=1.0, device="cuda", log=None, noise_source=None, stats=None):
+               bpp_limit=1.0, device="cuda", log=None, noise_source=None, stats=None, noise="torch"):
     """The reference's sweep, batched.
 
     decoder:       ClipDecoder (only ``generate`` is used: the generator does not depend on q)
@@ -124,11 +143,26 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
     noise_source:  optional ``fn(job, round, step, shape) -> tensor`` (job = (vid, q, thr); step 0 = x_T, step i+1 = the
                    noise of sampler step i) replacing the per-job device generators -- parity tests inject the noise the
                    CPU oracle loop uses
+    noise:         "torch" -- one seeded ``torch.Generator`` per (job, round, step) -- or "evc": noise specification N1
+                   (DESIGN.md section 5), one ``evc_noise_normal_f32`` launch per step keyed by (seed, stream id = the job's
+                   number, start frame = frames the job holds when the round starts, step).  Only "evc" can be replayed
+                   by a receiver (container.pack_job / ClipDecoder.decode_jobs); ``noise_source`` wins over both
     stats:         optional dict, filled with the launch-size histogram {batch size: generation launches}, the number of
-                   generation rounds and of key frames coded
-    Returns {(vid, q): [dict(thr, x (frames,3,H,W) float32 numpy, d (frames,) int, bits [..], bpp)]} with, per (vid, q),
-    the thresholds in the given order cut at the first one whose rate reaches ``bpp_limit`` bits per pixel
-    (``if NN_bpp >= 1.0: break``, city_sender.py:563-564)."""
+                   generation rounds and of key frames coded, and the host seconds spent drawing noise
+    Returns {(vid, q): [dict(thr, x (frames,3,H,W) float32 numpy, d (frames,) int, bits [..], bpp, segments, stream_id,
+    seed, key_strings, shape)]} with, per (vid, q), the thresholds in the given order cut at the first one whose rate reaches
+    ``bpp_limit`` bits per pixel (``if NN_bpp >= 1.0: break``, city_sender.py:563-564).  ``segments`` is the job's program in
+    order: ("key", n) for n key frames decoded in one ELIC call (the initial pair, each fall-back pair, 1 at the clip's
+    end), ("gen", n) for a round of which n >= 1 frames were kept (a rejected round leaves no frame and no entry: its noise
+    key is never reused, because the fall-back moves the start frame on); ``key_strings`` the key frames' strings in order."""
+    if noise not in ("torch", "evc"):
+        raise ValueError(f"noise must be 'torch' or 'evc', not {noise!r}")
+    if noise == "evc" and noise_source is None:
+        cfg = decoder.config
+        if getattr(cfg.model, "gamma", False):
+            raise NotImplementedError("noise='evc': noise specification N1 defines Gaussian noise only (config.model.gamma is set)")
+        if float(getattr(cfg.sampling, "t_min", -1) or -1) > 0:
+            raise NotImplementedError("noise='evc': noise specification N1 has no draw for a t_min > 0 start")
     jobs, uid = [], 0
     for vid in clips:
         for q in qs:
@@ -137,7 +171,8 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
                 uid += 1
     gt_dev = {vid: c.to(device=device, dtype=torch.float32) for vid, c in clips.items()}
     H, W = next(iter(clips.values())).shape[-2:]
-    key_cache = {}                  # (vid, q, frame) -> (x_hat on device, bits)
+    key_cache = {}                  # (vid, q, frame) -> (x_hat on device, bits, strings)
+    shapes = []                     # hyper-latent shape of every ELIC call (all equal: one frame size)
 
     def ensure_keys(wanted):
         """Code every missing (vid, q, frame) of ``wanted``: one batched ELIC encode + decode per q."""
@@ -146,20 +181,27 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
             for c0 in range(0, len(todo), max_batch):
                 part = todo[c0:c0 + max_batch]
                 x = torch.stack([gt_dev[v][f] for (v, _, f) in part], 0)
-                xh, bits = inference_batch(models[q], x, patch)
+                xh, bits, strings, shape = coded_batch(models[q], x, patch)
+                shapes.append(tuple(shape))
                 for i, k in enumerate(part):
-                    key_cache[k] = (xh[i], bits[i])
+                    key_cache[k] = (xh[i], bits[i], strings[i])
 
     def add_keys(job, fs):
         for f in fs:
-            xh, b = key_cache[(job.vid, job.q, f)]
-            job.x.append(xh); job.bits.append(b); job.d.append(1)
+            xh, b, st = key_cache[(job.vid, job.q, f)]
+            job.x.append(xh); job.bits.append(b); job.d.append(1); job.strings.append(st)
+        if len(fs):
+            job.segments.append(("key", len(fs)))
 
     ensure_keys({(j.vid, j.q, f) for j in jobs for f in (0, 1)})          # city_sender.py:521-524
     for j in jobs:
         add_keys(j, (0, 1))
 
-    def noise_for(batch):
+    def _noise_for(batch):
+        if noise == "evc" and noise_source is None:      # the round's keys go up once; one launch per step for the whole batch
+            keys = L.noise_keys([(j.uid, len(j.x)) for j in batch], device)
+            return lambda tag, shape: L.noise_normal(keys, shape, seed, 0 if tag == "init" else int(tag) + 1)
+
         def fn(tag, shape):      # one counter-based stream per (job, round, step): independent of the batch composition
             step = 0 if tag == "init" else int(tag) + 1
             out = torch.empty(shape, device=device, dtype=torch.float32)
@@ -173,6 +215,18 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
                 out[i] = torch.randn(shape[1:], device=device, dtype=torch.float32, generator=g)
             return out
         return fn
+
+    def noise_for(batch):
+        fn = _noise_for(batch)
+        if stats is None:
+            return fn
+
+        def timed(tag, shape):       # host time spent drawing noise (launches are asynchronous: this is the CPU's share)
+            t0 = time.perf_counter()
+            out = fn(tag, shape)
+            stats["noise_host_seconds"] = stats.get("noise_host_seconds", 0.0) + time.perf_counter() - t0
+            return out
+        return timed
 
     while True:
         active = [j for j in jobs if len(j.x) < frames]
@@ -199,6 +253,8 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
                     j.x.append(pred[k, t]); j.d.append(0); acc += 1
                 o += n_new[k]
                 j.round += 1
+                if acc:
+                    j.segments.append(("gen", acc))
                 if acc == 0:
                     fallback.append(j)
         if fallback:                 # city_sender.py:538-548: key-code the next two frames
@@ -221,7 +277,8 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
             lst.append(None)
             continue
         lst.append(dict(thr=j.thr, x=torch.stack(j.x[:frames], 0).cpu().numpy(), d=np.asarray(j.d[:frames], dtype=np.int64),
-                        bits=list(j.bits), bpp=bpp))
+                        bits=list(j.bits), bpp=bpp, segments=list(j.segments), stream_id=j.uid, seed=int(seed),
+                        key_strings=list(j.strings), shape=shapes[0]))
     return {k: [r for r in v if r is not None] for k, v in out.items()}
 
 

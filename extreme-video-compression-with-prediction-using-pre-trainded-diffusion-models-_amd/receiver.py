@@ -1,0 +1,140 @@
+"""Receiver for policy-coded clips: decodes the job streams a ``city_sender.py --policy psnr|lpips --bitstream-dir DIR`` run
+wrote (container format 3, one file per reported (video, q, threshold) job) with nothing but the model files.
+
+    python city_receiver.py --bitstream-dir DIR --output_path OUT [--config ... --exp ... --ckpt ... -p ... | --synthetic]
+
+The reference has no receiver (its generator runs inside the sender, city_sender.py:521-550).  What it implies is restated in
+``ClipDecoder.decode_jobs``: the stream carries the job's program -- which frames are key frames, where each generation round
+was cut -- and the key of its noise (noise specification N1), so the receiver generates from the same
+decoded frames, in the same chunks, with the same noise as the sender judged.  The sampler, its step count and the denoise
+flag are read from the streams; only the ELIC models the streams name are loaded.  One process, one GPU.
+"""
+import argparse
+import glob
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import container
+
+
+def write_job_streams(directory, results, models, sampler, cfg):
+    """Sender side: one ``job_v<vid>_q<q>_thr<thr>.evc`` per reported job of ``policy.run_policy(..., noise="evc")``.
+    results: its return value; sampler: "DDPM" | "DDIM" | "FPNDM"; cfg: the generator's config.  -> {(vid, q, thr): path}."""
+    os.makedirs(directory, exist_ok=True)
+    paths = {}
+    for (vid, q), lst in results.items():
+        for r in lst:
+            blob = container.pack_job(r["segments"], r["key_strings"], r["shape"], models[q].codec_tag(), r["seed"],
+                                      r["stream_id"], vid, q, r["thr"], sampler, getattr(cfg.sampling, "subsample", None) or 0,
+                                      cfg.sampling.denoise)
+            path = os.path.join(directory, container.job_file_name(vid, q, r["thr"]))
+            with open(path, "wb") as fh:
+                fh.write(blob)
+            paths[(vid, q, r["thr"])] = path
+    return paths
+
+
+def read_job_streams(directory):
+    """-> [(path, bytes)] of every job_*.evc in ``directory``, sorted by name."""
+    out = []
+    for path in sorted(glob.glob(os.path.join(directory, "job_*.evc"))):
+        with open(path, "rb") as fh:
+            out.append((path, fh.read()))
+    return out
+
+
+def decode_streams(blobs, net, cfg, model_for, max_batch=32, range_recovery=None, log=print):
+    """blobs: [bytes]; model_for: q -> ElicModel (called once per q the streams name); -> ([job dict], [frames tensor]) in
+    the order given.  A stream coded under another entropy arithmetic raises ``container.CodecMismatch``."""
+    import copy
+    from . import sampler as S
+    from .decoder import ClipDecoder
+    jobs = [container.unpack_job(b) for b in blobs]
+    models = {q: model_for(q) for q in sorted({j["q"] for j in jobs})}
+    jobs = [container.unpack_job(b, expect_codec=models[j["q"]].codec_tag()) for b, j in zip(blobs, jobs)]
+    frames = [None] * len(jobs)
+    decoders = []
+    for setting in sorted({(j["sampler"], j["subsample"], j["denoise"]) for j in jobs}):
+        c = copy.deepcopy(cfg)
+        c.sampling.subsample = setting[1] or None
+        c.sampling.denoise = setting[2]
+        dec = ClipDecoder(net, None, c, S.get_sampler(setting[0]), range_recovery=range_recovery, log=log)
+        decoders.append(dec)
+        idx = [i for i, j in enumerate(jobs) if (j["sampler"], j["subsample"], j["denoise"]) == setting]
+        for i, f in zip(idx, dec.decode_jobs([jobs[i] for i in idx], max_batch=max_batch, models=models)):
+            frames[i] = f
+    return jobs, frames, decoders
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--bitstream-dir", type=str, required=True, help="directory of job_*.evc files (city_sender.py --bitstream-dir)")
+    p.add_argument("--output_path", type=str, default="test_out/", help="decoded_v<vid>_q<q>_thr<thr>.npy are written here")
+    # the sender's model flags
+    p.add_argument("--config", type=str, default="configs/mine.yml", help="Path to the config file")
+    p.add_argument("--exp", type=str, default="checkpoints/sender", help="directory of checkpoint_<ckpt>.pt")
+    p.add_argument("--ckpt", type=int, default=900000, help="Model checkpoint # to load from")
+    p.add_argument("--config_mod", nargs="*", type=str, default="model.ngf=192 model.n_head_channels=192")
+    p.add_argument("-p", "--path", dest="paths", type=str, nargs="+", default=None, help="ELIC checkpoints (indexed by q)")
+    p.add_argument("--synthetic", action="store_true", help="seeded stand-ins for missing checkpoints / data")
+    p.add_argument("--seed", type=int, default=1234, help="seed of the synthetic stand-ins (the sender's --seed)")
+    p.add_argument("--range-recovery", choices=["off", "layer"], default=None, help="as city_sender.py")
+    p.add_argument("--batch", type=int, default=32, help="jobs stacked per score-network launch")
+    p.add_argument("--data_npy", type=str, default="city_bonn.npy", help="original clips: when present, per-job PSNR is printed")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    from . import ckpt, cli, config as C, lib as L, synthetic
+    from .elic import ElicModel
+    from .scorenet import build_score_network
+    paths = args.paths or cli.DEFAULT_PATHS
+    streams = read_job_streams(args.bitstream_dir)
+    if not streams:
+        sys.exit(f"no job_*.evc under {args.bitstream_dir}")
+    cfg, _ = C.load_config(args.config, args.config_mod)
+    cfg.sampling.ckpt_id = args.ckpt or cfg.sampling.ckpt_id
+    device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cuda"
+    L.hip_lib()
+    ck = os.path.join(args.exp, f"checkpoint_{cfg.sampling.ckpt_id}.pt")
+    if os.path.exists(ck):
+        sd_d = ckpt.load_diffusion_checkpoint(ck, ema=cfg.model.ema)
+    elif args.synthetic:
+        sd_d = synthetic.diffusion_state_dict(cfg, args.seed)
+    else:
+        sys.exit(f"missing {ck} (pass --synthetic for seeded stand-in weights)")
+    net = build_score_network(cfg, sd_d, device=device)
+
+    def model_for(q):
+        if q < len(paths) and os.path.exists(paths[q]):
+            return ElicModel(ckpt.load_elic_state_dict(paths[q]), device=device)
+        if args.synthetic:
+            return ElicModel(synthetic.elic_state_dict(q), device=device)
+        sys.exit(f"missing ELIC checkpoint for q{q} (pass --synthetic)")
+
+    log = lambda m: print(m, flush=True)  # noqa: E731
+    jobs, frames, decoders = decode_streams([b for _, b in streams], net, cfg, model_for, max_batch=max(1, args.batch),
+                                            range_recovery=args.range_recovery, log=log)
+    data = np.load(args.data_npy, mmap_mode="r") if os.path.exists(args.data_npy) else None
+    os.makedirs(args.output_path, exist_ok=True)
+    note = cli.recovery_note(decoders[0])
+    for (path, _), job, x in zip(streams, jobs, frames):
+        name = "v%d_q%d_thr%.2f" % (job["vid"], job["q"], job["thr"])
+        cli.check_numerics(x, f"{os.path.basename(path)}", note)
+        x = x.cpu().numpy()
+        np.save(os.path.join(args.output_path, f"decoded_{name}.npy"), x)
+        line = f"{os.path.basename(path)}: {job['frames']} frames, {int(job['d'].sum())} key frames, " \
+               f"{container.payload_bits(job['key_strings'])} bits, {job['sampler']}-{job['subsample']}"
+        if data is not None:
+            gt = np.asarray(data[job["vid"]], dtype=np.float32) / 255.0
+            line += " PSNR %.3f" % np.mean([cli.cal_psnr(x[t], gt[t]) for t in range(len(x))])
+        log(line)
+    log(f"decoded {len(jobs)} job stream(s) into {args.output_path}")
+
+
+if __name__ == "__main__":
+    main()

@@ -422,6 +422,17 @@ long long evc_gdn_workspace_bytes(int B, int H, int W, int C);
 int evc_gdn_f32(const float* x, const void* gamma_packed, int arith, const float* beta, float* out, float* ws, int B,
                 int H, int W, int C, int inverse, int simplified, void* stream);
 
+/* ---- Noise specification N1: the replayable noise of the job streams (csrc/noise.hip) -------
+ * One launch fills the noise of one sampler step for a batch; every sample draws from its own counter-based stream, so its
+ * numbers depend on its key only, not on its row in the batch or on B.  out: [B][n] fp32, n % 4 == 0 (the sample's element
+ * count, 15*H*W for a chunk); keys: device array [B][2] = (stream id, start frame).  Philox4x32-10 with key = (seed low 32
+ * bits, seed high 32 bits) and counter = (j, step, start frame, stream id), j = index of the 4-element block inside the
+ * sample; step 0 is x_T, step i + 1 the noise of sampler step i.  The block's words w0..w3 give elements 4j .. 4j+3:
+ * u = ((w >> 9) + 0.5) * 2^-23, r = sqrt(-2 ln u(w0)), theta = 2 pi u(w1) -> r cos theta, r sin theta; the same from
+ * (w2, w3).  raw != 0 writes the four words bit-cast instead of the normals. */
+int evc_noise_normal_f32(float* out, const unsigned* keys, int B, long long n, unsigned long long seed, unsigned step,
+                         int raw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

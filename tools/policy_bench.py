@@ -7,7 +7,11 @@ chunk).  Synthetic clips, seeded weights of the reference architecture, the PSNR
 are not available offline); thresholds are spread over the PSNR range the generated frames actually reach, so that the
 sweep contains both accepted chunks and key-frame fall-backs like a real one.
 
-    python tools/policy_bench.py [--videos 1] [--subsample 100] [--max-batch 32] > profiles/r03_policy_bench.json
+    python tools/policy_bench.py [--videos 1] [--subsample 100] [--max-batch 32] [--noise torch|evc] > profiles/r03_policy_bench.json
+
+``--noise evc`` runs the sweep on the replayable noise of specification N1 (one HIP launch per sampler step for the whole batch)
+instead of one seeded torch.Generator per (job, round, step); the JSON line also reports the host seconds spent drawing noise and
+the noise kernel's write rate at B = 32.
 """
 import argparse
 import json
@@ -34,6 +38,7 @@ def main():
     ap.add_argument("--max-batch", type=int, default=32)
     ap.add_argument("--qs", type=int, nargs="+", default=[4, 5])             # city_sender.py:504 q range of the sweep
     ap.add_argument("--n-thresholds", type=int, default=28)                  # city_sender.py:505-508
+    ap.add_argument("--noise", choices=["torch", "evc"], default="torch")
     a = ap.parse_args()
     L.hip_lib()
     cfg = default_config(192, 192, 128, subsample=a.subsample)
@@ -52,10 +57,22 @@ def main():
     torch.cuda.synchronize()
     stats = {}
     t0 = time.perf_counter()
-    res = P.run_policy(dec, models, clips, a.qs, thresholds, P.PsnrMetric(), max_batch=a.max_batch, stats=stats,
+    res = P.run_policy(dec, models, clips, a.qs, thresholds, P.PsnrMetric(), max_batch=a.max_batch, stats=stats, noise=a.noise,
                        log=lambda m: print(f"[policy_bench {time.strftime('%H:%M:%S')}] {m}", file=sys.stderr, flush=True))
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    # the noise kernel alone: one sampler step of a full launch, B = 32 samples of 15 x 128 x 128 (31 MB written)
+    keys = L.noise_keys([(i, 2) for i in range(32)], "cuda")
+    buf = torch.empty((32, 15, 128, 128), device="cuda")
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for _ in range(5):
+        L.noise_normal(keys, buf.shape, 1234, 1, out=buf)
+    ev[0].record()
+    for i in range(100):
+        L.noise_normal(keys, buf.shape, 1234, i, out=buf)
+    ev[1].record()
+    torch.cuda.synchronize()
+    noise_us = ev[0].elapsed_time(ev[1]) * 1e3 / 100
     jobs = a.videos * len(a.qs) * len(thresholds)
     kept = sum(len(v) for v in res.values())
     gen = sum(int((r_["d"] == 0).sum()) for v in res.values() for r_ in v)
@@ -65,7 +82,9 @@ def main():
     print(json.dumps({
         "workload": f"{a.videos} video(s) x q {a.qs} x {len(thresholds)} PSNR thresholds = {jobs} sender jobs of 30 frames "
                     f"(city_sender.py:495-607), DDPM-{a.subsample}, full-size network, synthetic clips / seeded weights",
-        "seconds": round(el, 2), "jobs": jobs, "jobs_per_s": round(jobs / el, 3),
+        "noise": a.noise, "seconds": round(el, 2), "noise_host_seconds": round(stats.get("noise_host_seconds", 0.0), 3),
+        "noise_kernel_b32_us": round(noise_us, 2), "noise_kernel_b32_tb_per_s": round(buf.numel() * 4 / noise_us / 1e6, 3),
+        "jobs": jobs, "jobs_per_s": round(jobs / el, 3),
         "decoded_frames_per_s": round(jobs * 30 / el, 2),
         "jobs_below_1bpp": kept, "generated_frames_kept": gen,
         "generation_rounds": stats.get("rounds"), "generation_launches": launches,
