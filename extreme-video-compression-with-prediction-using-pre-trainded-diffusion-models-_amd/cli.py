@@ -13,7 +13,7 @@ the explicit fallback ``mask`` (fixed transmit mask) runs and the CLI says so; `
 absent.  ``--fvd`` (or ``i3d_pretrained_400.pt`` found where the reference keeps it, ``find_i3d_weights``) adds the
 reference's third per-job number, the FVD of the decoded clip against the original (city_sender.py:575-589), computed by the
 HIP I3D network (fvd.py) and saved as ``fvd_<idx>.npy``.  Under a decision rule ``--bitstream-dir DIR`` writes one replayable
-job stream per reported job (container format 3) for ``city_receiver.py`` and runs the sweep on noise specification N1
+job stream per reported job (container format 3; format 4 with ``--batch-invariant``) for ``city_receiver.py`` and runs the sweep on noise specification N1
 (``--noise evc``).  ``--gpus N`` (or ``torch.distributed.run``) block-shards the video range over N ranks, one GPU each.
 """
 import argparse
@@ -80,12 +80,18 @@ def build_parser():
     p.add_argument("--bitstream-dir", type=str, default=None,
                    help="mask policy: write each batch's key-frame strings + mask as an EVC1 container here and "
                         "decode from the bytes read back (container.py); psnr / lpips policy: write one job stream "
-                        "job_v<vid>_q<q>_thr<thr>.evc per reported job (container format 3) for city_receiver.py -- the "
+                        "job_v<vid>_q<q>_thr<thr>.evc per reported job (container format 3, or 4 with --batch-invariant) for city_receiver.py -- the "
                         "sweep then runs on the replayable noise (--noise evc)")
     p.add_argument("--noise", choices=["torch", "evc"], default=None,
                    help="psnr / lpips policy: torch (default) = one seeded torch.Generator per (job, round, step); evc = noise "
                         "specification N1 drawn by one HIP launch per step (DESIGN.md section 5), the only noise a receiver "
                         "can replay: --bitstream-dir selects it")
+    p.add_argument("--batch-invariant", action="store_true",
+                   help="psnr / lpips policy: generate in the score network's batch-invariant mode (DESIGN.md section 4): a "
+                        "job's frames do not depend on the launches it rides in, so city_receiver.py reproduces them bit for "
+                        "bit at any --batch.  Job streams are then container format 4 (plan revision + CRC-32 of the frames). "
+                        "Needs the replayable noise (--noise evc, selected when --noise is not given); refuses "
+                        "--range-recovery layer")
     p.add_argument("--range-recovery", choices=["off", "layer"], default=None,
                    help="layer: when a chunk raises an fp16-split range event, demote only the layers that raised it to the "
                         "bf16x6 split and regenerate the chunk with the same noise (default: EVC_RANGE_RECOVERY, else off: "
@@ -199,6 +205,19 @@ def main(argv=None):
     from .scorenet import build_score_network
 
     resolve_policy(args, log=lambda m: print(m, flush=True))
+    if args.batch_invariant:
+        from .recovery import recovery_mode
+        if args.policy == "mask":
+            sys.exit("--batch-invariant applies to the psnr / lpips policy sweep (the mask policy decodes fixed batches)")
+        if args.noise == "torch":
+            sys.exit("--batch-invariant with --noise torch: nobody can replay torch's generators, so there is no receiver to "
+                     "reproduce the frames; drop --noise or pass --noise evc")
+        if recovery_mode(args.range_recovery) == "layer":
+            sys.exit("--batch-invariant does not combine with --range-recovery layer: one sample's range event would demote "
+                     "layers for every sample and for the rest of the run, and a receiver could not know which")
+        if args.noise is None:
+            print("noise: evc (specification N1) because --batch-invariant frames are meant to be reproduced", flush=True)
+            args.noise = "evc"
     if args.policy != "mask":
         if args.bitstream_dir and args.noise == "torch":
             sys.exit("--bitstream-dir with --noise torch: a job stream whose frames depend on torch's generators cannot be "
@@ -344,7 +363,7 @@ def main(argv=None):
         clips = {vid: torch.from_numpy(np.asarray(data[vid], dtype=np.float32) / 255.0) for vid in vids}
         res = P.run_policy(dec, models, clips, args.q, thresholds, metric, patch=args.patch, max_batch=args.policy_batch,
                            seed=args.seed, device=device, bpp_limit=args.bpp_limit, log=lambda m: print(f"[rank {rank}] {m}", flush=True),
-                           noise=args.noise)
+                           noise=args.noise, batch_invariant=args.batch_invariant)
         if args.bitstream_dir:       # one replayable stream per reported job (receiver.py decodes them)
             from .receiver import write_job_streams
             written = write_job_streams(args.bitstream_dir, res, models, args.sampler, cfg)

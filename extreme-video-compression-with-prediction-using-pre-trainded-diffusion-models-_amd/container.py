@@ -17,9 +17,11 @@ a receiver whose networks run another arithmetic must REFUSE the stream (``Codec
 The payload bytes are exactly the strings the codec produced, so ``8 * payload`` equals the reference's bit count.
 
 Format 3 (``pack_job`` / ``unpack_job``, further down) is the stream of ONE policy job: its program of key / generated
-segments and the key of its noise, so that a receiver replays exactly what the sender judged.
+segments and the key of its noise, so that a receiver replays exactly what the sender judged.  Format 4 is format 3 for a
+job generated in batch-invariant mode: it adds the generation plan (id, revision) and a CRC-32 of the sender's frames.
 """
 import struct
+import zlib
 
 import numpy as np
 
@@ -120,7 +122,22 @@ def unpack(blob, expect_codec=None):
 #
 # ("key", n): n key frames decoded in one ELIC call; ("gen", n): one generation round from the last two decoded frames of
 # which the first n frames are kept, its noise keyed by (seed, stream id, start frame = frames decoded so far, step).
+#
+# Format 4 = format 3 for a job whose frames were generated in BATCH-INVARIANT mode: a receiver then
+# reproduces the sender's frames bit for bit at any batch size, so the stream also names the arithmetic that promise holds
+# for and carries a checksum to verify it.  Between the head above (through n_segments) and the segment list it inserts
+#
+#                  | u8 generation plan id (1 = PLAN_INVARIANT) | u16 plan revision | u32 CRC-32 of the sender's frames
+#
+# plan revision = ``lib.invariant_plan_revision()`` of the sender's library (bumped whenever a kernel change alters the bits
+# of invariant mode); the CRC is ``zlib.crc32`` of the job's decoded frames (frames, 3, H, W) as C-contiguous float32 bytes.
+# A receiver refuses an unknown plan id, or another revision (``PlanMismatch``), as it refuses a foreign codec tag.  Jobs
+# generated in the default mode keep writing format 3, byte for byte.
 FORMAT_JOB = 3
+FORMAT_JOB_INVARIANT = 4
+PLAN_INVARIANT = 1
+PLANS = {PLAN_INVARIANT: "batch-invariant"}
+_PLAN_HEAD = "<BHI"                # plan id, plan revision, frames CRC-32
 NOISE_N1 = 1
 NOISE_SPECS = {NOISE_N1: "N1"}
 SAMPLER_IDS = {"DDPM": 0, "DDIM": 1, "FPNDM": 2}
@@ -128,6 +145,15 @@ SAMPLER_NAMES = {v: k for k, v in SAMPLER_IDS.items()}
 SEGMENT_KINDS = ("key", "gen")
 CHUNK = 5                          # frames of one generation round
 _JOB_HEAD = "<BQIIBfBHBHHHHH"      # noise spec ... n_segments
+
+
+class PlanMismatch(ValueError):
+    """The stream's frames were generated under a generation plan (or a revision of it) this build does not reproduce."""
+
+
+def frames_crc(x):
+    """CRC-32 of decoded frames (frames, 3, H, W) as C-contiguous float32 bytes: what a format-4 stream carries."""
+    return zlib.crc32(np.ascontiguousarray(np.asarray(x), dtype=np.float32).tobytes()) & 0xFFFFFFFF
 
 
 def check_segments(segments, frames, n_key=None):
@@ -154,16 +180,23 @@ def check_segments(segments, frames, n_key=None):
 
 
 def pack_job(segments, key_strings, shape, codec, seed, stream_id, vid, q, thr, sampler, subsample, denoise,
-             noise_spec=NOISE_N1):
-    """One policy job -> bytes.  segments: [("key" | "gen", n)]; key_strings: per key frame, in order, ``[y_strings[5][2][1],
+             noise_spec=NOISE_N1, plan=None, crc=None):
+    """One policy job -> bytes.  ``plan`` = (plan id, plan revision) and ``crc`` = ``frames_crc`` of the sender's frames make it
+    a format-4 stream (a job generated in batch-invariant mode); without them it is format 3.  segments: [("key" | "gen", n)]; key_strings: per key frame, in order, ``[y_strings[5][2][1],
     z_strings[1]]`` (one clip); codec: ``ElicModel.codec_tag()`` of the encoder; sampler: "DDPM" | "DDIM" | "FPNDM"."""
     segments = [(str(k), int(n)) for k, n in segments]
     frames = sum(n for _, n in segments)
     check_segments(segments, frames, len(key_strings))
-    out = [MAGIC, struct.pack("<BBH", FORMAT_JOB, int(codec[0]), int(codec[1])),
+    if (plan is None) != (crc is None):
+        raise ValueError("a format-4 job stream needs both its generation plan and the CRC of the sender's frames")
+    if plan is not None and int(plan[0]) not in PLANS:
+        raise ValueError(f"unknown generation plan id {plan[0]}")
+    out = [MAGIC, struct.pack("<BBH", FORMAT_JOB if plan is None else FORMAT_JOB_INVARIANT, int(codec[0]), int(codec[1])),
            struct.pack(_JOB_HEAD, int(noise_spec), int(seed) & (2 ** 64 - 1), int(stream_id), int(vid), int(q), float(thr),
                        SAMPLER_IDS[sampler], int(subsample), int(bool(denoise)), frames, int(shape[0]), int(shape[1]),
                        len(key_strings), len(segments))]
+    if plan is not None:
+        out.append(struct.pack(_PLAN_HEAD, int(plan[0]), int(plan[1]), int(crc) & 0xFFFFFFFF))
     out += [struct.pack("<BB", SEGMENT_KINDS.index(k), n) for k, n in segments]
     for ys, zs in key_strings:
         assert len(zs) == 1, "a job stream holds one clip"
@@ -174,15 +207,19 @@ def pack_job(segments, key_strings, shape, codec, seed, stream_id, vid, q, thr, 
     return b"".join(out)
 
 
-def unpack_job(blob, expect_codec=None):
-    """bytes of ``pack_job`` -> dict(codec, noise_spec, seed, stream_id, vid, q, thr, sampler, subsample, denoise, frames,
-    shape, segments, d, key_strings).  Raises ValueError for anything but a complete, consistent format-3 stream of a known
-    noise specification, ``CodecMismatch`` for a stream coded under another arithmetic / kernel revision."""
+def unpack_job(blob, expect_codec=None, expect_plan_revision=None):
+    """bytes of ``pack_job`` -> dict(format, codec, noise_spec, seed, stream_id, vid, q, thr, sampler, subsample, denoise,
+    frames, shape, segments, d, key_strings, plan, crc); ``plan`` = (id, revision) and ``crc`` of a format-4 stream, None for
+    format 3.  Raises ValueError for anything but a complete, consistent format-3 / format-4 stream of a known noise
+    specification and generation plan, ``CodecMismatch`` for a stream coded under another arithmetic / kernel revision,
+    ``PlanMismatch`` for a format-4 stream of another plan revision than ``expect_plan_revision`` (the receiver's
+    ``lib.invariant_plan_revision()``; None = not checked)."""
     if blob[:4] != MAGIC or len(blob) < 8:
         raise ValueError("not an EVC1 container")
     fmt, arith, rev = struct.unpack_from("<BBH", blob, 4)
-    if fmt != FORMAT_JOB:
-        raise ValueError(f"not a job stream: EVC1 container format {fmt} (job streams are format {FORMAT_JOB})")
+    if fmt not in (FORMAT_JOB, FORMAT_JOB_INVARIANT):
+        raise ValueError(f"not a job stream: EVC1 container format {fmt} (job streams are formats {FORMAT_JOB} and "
+                         f"{FORMAT_JOB_INVARIANT})")
     if expect_codec is not None and (arith, rev) != tuple(int(v) for v in expect_codec):
         raise CodecMismatch(f"stream was coded with convolution arithmetic {ARITH_NAMES.get(arith, arith)} rev {rev}, this "
                             f"receiver runs {ARITH_NAMES.get(int(expect_codec[0]), expect_codec[0])} rev {int(expect_codec[1])}: "
@@ -198,6 +235,19 @@ def unpack_job(blob, expect_codec=None):
                          f"{', '.join(NOISE_SPECS.values())})")
     if sampler not in SAMPLER_NAMES:
         raise ValueError(f"corrupt job stream: unknown sampler id {sampler}")
+    plan = crc = None
+    if fmt == FORMAT_JOB_INVARIANT:
+        if off + struct.calcsize(_PLAN_HEAD) > len(blob):
+            raise ValueError("truncated job stream")
+        plan_id, plan_rev, crc = struct.unpack_from(_PLAN_HEAD, blob, off)
+        off += struct.calcsize(_PLAN_HEAD)
+        if plan_id not in PLANS:
+            raise PlanMismatch(f"unknown generation plan id {plan_id} (this build reproduces {sorted(PLANS)} = "
+                               f"{', '.join(PLANS.values())})")
+        if expect_plan_revision is not None and plan_rev != int(expect_plan_revision):
+            raise PlanMismatch(f"stream was generated under revision {plan_rev} of the {PLANS[plan_id]} plan, this receiver's "
+                               f"kernels are revision {int(expect_plan_revision)}: its frames would not be the sender's")
+        plan = (plan_id, plan_rev)
     if off + 2 * n_seg > len(blob):
         raise ValueError("truncated job stream")
     segments = []
@@ -227,7 +277,7 @@ def unpack_job(blob, expect_codec=None):
         key_strings.append([ys, zs])
     if off != len(blob):
         raise ValueError("trailing bytes in job stream")
-    return dict(codec=(arith, rev), noise_spec=spec, seed=seed, stream_id=stream_id, vid=vid, q=q, thr=thr,
+    return dict(format=fmt, plan=plan, crc=crc, codec=(arith, rev), noise_spec=spec, seed=seed, stream_id=stream_id, vid=vid, q=q, thr=thr,
                 sampler=SAMPLER_NAMES[sampler], subsample=subsample, denoise=bool(denoise), frames=frames, shape=(sh, sw),
                 segments=segments, d=d, key_strings=key_strings)
 

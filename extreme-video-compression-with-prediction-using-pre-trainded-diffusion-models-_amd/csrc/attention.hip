@@ -214,7 +214,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_f16_kernel(const floa
                                                                       int kparts, int tiles_per_part,
                                                                       float* __restrict__ part_o,
                                                                       float* __restrict__ part_ml,
-                                                                      const char* __restrict__ kv_planes) {
+                                                                      const char* __restrict__ kv_planes,
+                                                                      int bound_stride) {
     constexpr int NKS = D / 16;            // k-steps of the QK^T product
     constexpr int DT = D / 32;             // 32-wide d tiles of the PV product
     constexpr int NT = 64 * WAVES;
@@ -240,9 +241,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_f16_kernel(const floa
     const bool qvalid = myq < N;
 
     // operand scales (powers of two): bound * scale in [2^9, 2^10) -> at most 1024, far above fp16's subnormals
-    const float sq = pow2_scale_for(__uint_as_float(bounds[0]), 9);
-    const float sk = pow2_scale_for(__uint_as_float(bounds[1]), 9);
-    const float sv = pow2_scale_for(__uint_as_float(bounds[2]), 9);
+    const unsigned* const bw = bounds + b * bound_stride;      // batch-invariant mode: the sample's own three words
+    const float sq = pow2_scale_for(__uint_as_float(bw[0]), 9);
+    const float sk = pow2_scale_for(__uint_as_float(bw[1]), 9);
+    const float sv = pow2_scale_for(__uint_as_float(bw[2]), 9);
     constexpr float SP = 1024.0f;                     // softmax weights are in [0, 1]
     const float s_mul = scale / (sq * sk);            // accumulator -> logits
     const float o_mul = 1.0f / (SP * sv);             // accumulator -> sum_k p_k v_k
@@ -476,7 +478,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void attention_f16_kernel(const floa
 template <int D>
 __global__ __launch_bounds__(256) void attention_kv_planes_kernel(const float* __restrict__ k, const float* __restrict__ v,
                                                                   int ld, int N, const unsigned* __restrict__ bounds,
-                                                                  char* __restrict__ planes) {
+                                                                  char* __restrict__ planes, int bound_stride) {
     constexpr int NT = 256;
     constexpr int KROW = 2 * D + 16, VROW = 64 + 16;
     constexpr int KPL = 32 * KROW, VPL = D * VROW;
@@ -492,8 +494,8 @@ __global__ __launch_bounds__(256) void attention_kv_planes_kernel(const float* _
         char* row = i < 64 ? Ks + i * KROW + 2 * D : Vs + (i - 64) * VROW + 64;
         *reinterpret_cast<float4*>(row) = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    const float sk = pow2_scale_for(__uint_as_float(bounds[1]), 9);
-    const float sv = pow2_scale_for(__uint_as_float(bounds[2]), 9);
+    const float sk = pow2_scale_for(__uint_as_float(bounds[b * bound_stride + 1]), 9);
+    const float sv = pow2_scale_for(__uint_as_float(bounds[b * bound_stride + 2]), 9);
     // all loads first (they are independent: one memory round trip instead of one per unit), then convert + place
     constexpr int KU = (32 * (D / 8) + NT - 1) / NT;             // K unit = (key, 8-channel chunk)
     constexpr int VU = (8 * D + NT - 1) / NT;                     // V unit = (4 consecutive keys, channel d), lanes along d
@@ -646,8 +648,11 @@ int g_attn_pre = 1;       // run-time switch (evc_attention_set_option "kv_plane
 int g_attn_f16_min_keys = 128;   // run-time switch "f16_min_keys": fewest keys for which the fp16-split kernel is used
 
 // bytes of the key-part buffers at the head of the workspace (part_o | part_ml), rounded to 16
-long long attention_parts_bytes(int B, int heads, int N, int D) {
-    const int kp = attention_plan(B, heads, N, true).kparts, kp16 = attention_plan_f16(B, heads, N).kparts;
+// (`inv`: batch-invariant mode plans at the reference batch EVC_INVARIANT_REF_BATCH of include/evc_hip.h, whatever B is:
+// waves and key parts from (heads, N, D) only)
+long long attention_parts_bytes(int B, int heads, int N, int D, bool inv = false) {
+    const int Bp = inv ? EVC_INVARIANT_REF_BATCH : B;
+    const int kp = attention_plan(Bp, heads, N, true).kparts, kp16 = attention_plan_f16(Bp, heads, N).kparts;
     const int kparts = kp > kp16 ? kp : kp16;
     if (kparts <= 1) return 0;
     const long long n = (long long)kparts * B * N * heads * ((long long)D + 2) * (long long)sizeof(float);
@@ -676,13 +681,21 @@ int launch_f32(dim3 grid, size_t lds, hipStream_t st, const float* q, const floa
 
 template <int D>
 int launch(const float* q, const float* k, const float* v, int ld, float* out, int ld_out, int B, int heads, int N,
-           float scale, float* ws, const unsigned* bounds, hipStream_t st) {
+           float scale, float* ws, const unsigned* bounds, hipStream_t st, bool inv) {
     const size_t lds = (size_t)2 * 32 * (D + 4) * sizeof(float);
+    const int Bp = inv ? EVC_INVARIANT_REF_BATCH : B;        // the batch the plan is made for
+    const int bstride = inv ? 3 : 0;                         // per-sample bound words
+    // batch-invariant mode: always the with-workspace plan (the entry point guarantees a workspace wherever that plan uses
+    // one) and the default values of the process-wide A/B switches: the plan is a function of (heads, N, D) only
+    const bool have_ws = inv || ws != nullptr;
+    const int min_keys = inv ? 128 : g_attn_f16_min_keys;
+    const int pre = inv ? 1 : g_attn_pre;
     // head widths above 192 stay on the f32 kernel: the fp16 kernel keeps Q (both planes) and O in registers, D/2 + D/2 of them
     constexpr bool F16_OK = D <= 192;
-    const bool use_f16 = F16_OK && bounds && N >= g_attn_f16_min_keys;
-    const AttnPlan pl = (use_f16 && ws) ? attention_plan_f16(B, heads, N) : attention_plan(B, heads, N, ws != nullptr);
+    const bool use_f16 = F16_OK && bounds && N >= min_keys;
+    const AttnPlan pl = (use_f16 && have_ws) ? attention_plan_f16(Bp, heads, N) : attention_plan(Bp, heads, N, have_ws);
     const int waves = pl.waves;
+    if (!ws && (pl.kparts > 1 || (use_f16 && pre && waves == 4 && N >= 512 && inv))) return EVC_EINVAL;   // the plan needs a workspace
     float* part_o = ws;
     float* part_ml = ws ? ws + (size_t)pl.kparts * B * N * heads * D : nullptr;
     dim3 grid(((N + 32 * waves - 1) / (32 * waves)) * pl.kparts, heads, B);
@@ -693,10 +706,10 @@ int launch(const float* q, const float* k, const float* v, int ld, float* out, i
         // with a workspace: K / V converted once per launch into tile images (behind the key-part buffers), staged by LDS-DMA
         // (from 512 keys on: below that the pre-pass launch costs more than the conversions it saves -- B = 9, 256 keys, 3 heads:
         // 36 us with it, 29 without; 1024 keys, 2 heads: 110 vs 127 -- profiles/r04_attn_kv_planes_ab.log)
-        if (waves == 4 && ws && g_attn_pre && N >= 512) {
+        if (waves == 4 && ws && pre && N >= 512) {
             const int ntiles = (N + 31) / 32;
-            char* planes = reinterpret_cast<char*>(ws) + attention_parts_bytes(B, heads, N, D);
-            hipLaunchKernelGGL((attention_kv_planes_kernel<D>), dim3(ntiles, heads, B), dim3(256), lds16, st, k, v, ld, N, bounds, planes);
+            char* planes = reinterpret_cast<char*>(ws) + attention_parts_bytes(B, heads, N, D, inv);
+            hipLaunchKernelGGL((attention_kv_planes_kernel<D>), dim3(ntiles, heads, B), dim3(256), lds16, st, k, v, ld, N, bounds, planes, bstride);
             if (2 * lds16 > 64 * 1024) {
                 static unsigned long long done = 0;                   // one bit per device id
                 int dev = 0;
@@ -709,16 +722,16 @@ int launch(const float* q, const float* k, const float* v, int ld, float* out, i
                 }
             }
             hipLaunchKernelGGL((attention_f16_kernel<D, 4, true>), grid, dim3(256), 2 * lds16, st, q, k, v, ld, out, ld_out, N, scale,
-                               bounds, pl.kparts, pl.tiles_per_part, part_o, part_ml, planes);
+                               bounds, pl.kparts, pl.tiles_per_part, part_o, part_ml, planes, bstride);
         } else if (waves == 4)
             hipLaunchKernelGGL((attention_f16_kernel<D, 4>), grid, dim3(256), lds16, st, q, k, v, ld, out, ld_out, N, scale,
-                               bounds, pl.kparts, pl.tiles_per_part, part_o, part_ml, nullptr);
+                               bounds, pl.kparts, pl.tiles_per_part, part_o, part_ml, nullptr, bstride);
         else if (waves == 2)
             hipLaunchKernelGGL((attention_f16_kernel<D, 2>), grid, dim3(128), lds16, st, q, k, v, ld, out, ld_out, N, scale,
-                               bounds, pl.kparts, pl.tiles_per_part, part_o, part_ml, nullptr);
+                               bounds, pl.kparts, pl.tiles_per_part, part_o, part_ml, nullptr, bstride);
         else
             hipLaunchKernelGGL((attention_f16_kernel<D, 1>), grid, dim3(64), lds16, st, q, k, v, ld, out, ld_out, N, scale,
-                               bounds, pl.kparts, pl.tiles_per_part, part_o, part_ml, nullptr);
+                               bounds, pl.kparts, pl.tiles_per_part, part_o, part_ml, nullptr, bstride);
     }
     if (!use_f16) {
         const int rc = waves == 4 ? launch_f32<D, 4>(grid, lds, st, q, k, v, ld, out, ld_out, N, scale, pl.kparts, pl.tiles_per_part, part_o, part_ml)
@@ -741,17 +754,17 @@ int launch(const float* q, const float* k, const float* v, int ld, float* out, i
 
 static int attention_dispatch(const float* q, const float* k, const float* v, int ld_qkv, float* out, int ld_out,
                               int B, int heads, int N, int D, float scale, float* ws, const unsigned* bounds,
-                              void* stream) {
+                              void* stream, bool inv = false) {
     if (!q || !k || !v || !out || B <= 0 || heads <= 0 || N <= 0 || ld_qkv < heads * D || ld_out < heads * D)
         return EVC_EINVAL;
     if ((ld_qkv & 3) || (ld_out & 3)) return EVC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     switch (D) {
-        case 256: return launch<256>(q, k, v, ld_qkv, out, ld_out, B, heads, N, scale, ws, bounds, st);
-        case 192: return launch<192>(q, k, v, ld_qkv, out, ld_out, B, heads, N, scale, ws, bounds, st);
-        case 128: return launch<128>(q, k, v, ld_qkv, out, ld_out, B, heads, N, scale, ws, bounds, st);
-        case 64: return launch<64>(q, k, v, ld_qkv, out, ld_out, B, heads, N, scale, ws, bounds, st);
-        case 32: return launch<32>(q, k, v, ld_qkv, out, ld_out, B, heads, N, scale, ws, bounds, st);
+        case 256: return launch<256>(q, k, v, ld_qkv, out, ld_out, B, heads, N, scale, ws, bounds, st, inv);
+        case 192: return launch<192>(q, k, v, ld_qkv, out, ld_out, B, heads, N, scale, ws, bounds, st, inv);
+        case 128: return launch<128>(q, k, v, ld_qkv, out, ld_out, B, heads, N, scale, ws, bounds, st, inv);
+        case 64: return launch<64>(q, k, v, ld_qkv, out, ld_out, B, heads, N, scale, ws, bounds, st, inv);
+        case 32: return launch<32>(q, k, v, ld_qkv, out, ld_out, B, heads, N, scale, ws, bounds, st, inv);
         default: return EVC_EUNSUPPORTED;
     }
 }
@@ -761,13 +774,32 @@ extern "C" int evc_attention_f32(const float* q, const float* k, const float* v,
     return attention_dispatch(q, k, v, ld_qkv, out, ld_out, B, heads, N, D, scale, nullptr, nullptr, stream);
 }
 
-extern "C" long long evc_attention_workspace_bytes(int B, int heads, int N, int D) {
+static long long attention_ws_bytes(int B, int heads, int N, int D, bool inv) {
     if (B <= 0 || heads <= 0 || N <= 0 || D <= 0) return EVC_EINVAL;
-    long long n = attention_parts_bytes(B, heads, N, D);          // key-part buffers: one size serves both kernels
+    long long n = attention_parts_bytes(B, heads, N, D, inv);     // key-part buffers: one size serves both kernels
     // + the K / V tile images of the fp16 kernel (evc_attention_f16x3_f32 with >= 128 keys and a head width it covers)
     if (N >= 128 && D <= 192 && (D == 32 || D == 64 || D == 128 || D == 192))
         n += (long long)B * heads * ((N + 31) / 32) * (2LL * 32 * (2 * D + 16) + 2LL * D * 80);
     return n;
+}
+
+extern "C" long long evc_attention_workspace_bytes(int B, int heads, int N, int D) {
+    return attention_ws_bytes(B, heads, N, D, false);
+}
+
+extern "C" long long evc_attention_invariant_workspace_bytes(int B, int heads, int N, int D) {
+    return attention_ws_bytes(B, heads, N, D, true);
+}
+
+// Batch-invariant attention: the plan of the reference batch at every B (query blocks never straddle samples: grid z = B),
+// per-sample bound words, the A/B switches of evc_attention_set_option ignored.  launch() always takes the with-workspace
+// plan in this mode, so a workspace is required wherever that plan uses one (key parts, K / V tile images).
+extern "C" int evc_attention_invariant_f32(const float* q, const float* k, const float* v, int ld_qkv, float* out, int ld_out,
+                                           int B, int heads, int N, int D, float scale, const unsigned* bounds, float* ws,
+                                           void* stream) {
+    const long long need = attention_ws_bytes(B, heads, N, D, true);
+    if (need < 0 || (need > 0 && !ws)) return EVC_EINVAL;
+    return attention_dispatch(q, k, v, ld_qkv, out, ld_out, B, heads, N, D, scale, ws, bounds, stream, true);
 }
 
 extern "C" int evc_attention_set_option(const char* name, int value) {

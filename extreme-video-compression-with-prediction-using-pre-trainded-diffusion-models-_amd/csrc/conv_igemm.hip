@@ -87,6 +87,10 @@ struct ConvK {
     const char* x2_w;            // packed planes of the 1x1 weights (behind their header), nullptr = no fused operand
     const float* x2_hdr;         // their header: [0] = 1 / (activation scale * weight scale)
     const unsigned* x2_bound;
+    // Batch-invariant mode (evc_conv_args::invariant): bound_stride = 1 -> in_bound / x2_bound hold ONE word per sample and a
+    // pixel's scale comes from its own sample's word; generic_epi = 1 -> every tile takes the generic epilogue (set when a
+    // tile may straddle samples or be partial, so that no element's epilogue form depends on the batch).
+    int bound_stride, generic_epi;
 };
 
 // f16x3 on a source with no GroupNorm in front of it (raw residual stream, attention output): the caller supplies a bound
@@ -96,11 +100,17 @@ struct ConvK {
 // accumulator scale.  Wave-uniform, evaluated once per kernel.
 // A bound that is not finite (the NaN pattern the bound kernels write when a moment is NaN / inf) gives a NaN scale: the
 // operands, the accumulator scale and so the whole output are NaN -- a non-finite input never becomes finite numbers.
-__device__ __forceinline__ float in_scale(const ConvK& p) {
-    if (!p.in_bound) return 1.0f;
-    const float b = sqrtf(__uint_as_float(*p.in_bound));
+__device__ __forceinline__ float bound_scale(unsigned bits) {
+    const float b = sqrtf(__uint_as_float(bits));
     if (!(b < 3.0e38f)) return __builtin_nanf("");
     return b > 0.f ? ldexpf(1.0f, 6 - ilogbf(b)) : 1.0f;
+}
+// index of pixel m's bound word: 0, or its sample in batch-invariant mode (one word per sample)
+__device__ __forceinline__ int bound_index(const ConvK& p, int m) { return p.bound_stride ? min(m, p.M - 1) / p.HW : 0; }
+// `m`: a pixel of the tile (any one: tiles whose pixels could disagree take the per-pixel forms, see generic_epi)
+__device__ __forceinline__ float in_scale(const ConvK& p, int m) {
+    if (!p.in_bound) return 1.0f;
+    return bound_scale(p.in_bound[bound_index(p, m)]);
 }
 
 __device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
@@ -149,7 +159,7 @@ __device__ __forceinline__ void conv_epilogue_full(const ConvK& p, f32x16 (&acc)
     constexpr int BM = 32 * TM * WM;
     const int ws_m0 = tail ? p.tail_first * BM : 0;          // slab row 0 = this pixel
     const size_t ws_M = tail ? (size_t)p.tail_rows : (size_t)p.M;
-    const float ascale = p.w_hdr ? p.w_hdr[0] / in_scale(p) : 1.0f;
+    const float ascale = p.w_hdr ? p.w_hdr[0] / in_scale(p, m0) : 1.0f;
     const float oscale = p.out_scale;
     const int mw = m0 + wm * 32 * TM + 4 * half;
     const int cw = n0 + wn * 32 * TN + l31;
@@ -204,7 +214,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[TM][
     constexpr int BM = 32 * TM * WM;       // WM = waves along the pixel dimension (2, or 4 in the 8-wave row-reuse kernel)
     constexpr int BN = 64 * TN;
     const bool partial = p.splits > 1 || tail;
-    if (m0 + BM <= p.M && n0 + BN <= p.Co) {
+    if (!p.generic_epi && m0 + BM <= p.M && n0 + BN <= p.Co) {
 #define EVC_EPI(PA, RE, ST, AC) conv_epilogue_full<TM, TN, WM, PA, RE, ST, AC>(p, acc, m0, n0, split, wm, wn, l31, half, tail)
         if (partial) EVC_EPI(true, false, false, false);
         else if (p.act_out != EVC_ACT_NONE) EVC_EPI(false, true, true, true);
@@ -218,7 +228,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[TM][
     const int ws_m0 = tail ? p.tail_first * BM : 0;          // slab row 0 = this pixel
     const size_t ws_M = tail ? (size_t)p.tail_rows : (size_t)p.M;
     // f16x3: the operands were scaled by powers of two to sit in fp16's range; undo it here (exact)
-    const float ascale = p.w_hdr ? p.w_hdr[0] / in_scale(p) : 1.0f;
+    const float ascale = p.w_hdr ? p.w_hdr[0] / in_scale(p, m0) : 1.0f;
+    const bool per_row = p.bound_stride && p.in_bound;       // batch-invariant mode: the pixel's own sample's scale
     const int mw = m0 + wm * 32 * TM + 4 * half;
     const int cw = n0 + wn * 32 * TN + l31;
     {
@@ -233,7 +244,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvK& p, f32x16 (&acc)[TM][
                 for (int r = 0; r < 16; ++r) {
                     const int m = mw + i * 32 + (r & 3) + 8 * (r >> 2);
                     if (m >= p.M) continue;
-                    float v = acc[i][j][r] * ascale;
+                    float v = acc[i][j][r] * (per_row ? p.w_hdr[0] / in_scale(p, m) : ascale);
                     if (partial) {
                         p.ws[((size_t)split * ws_M + (m - ws_m0)) * p.Co + co] = v;
                     } else {
@@ -591,7 +602,7 @@ __global__ __launch_bounds__(256, 2) void conv_splitn_kernel(ConvK p) {
     };
     float4 areg[2] = {}, ca[2], cs[2];
     bool aok = false;
-    const float xscale = F16_ACT_SCALE * in_scale(p);      // used by the fp16 split only
+    const float xscale = F16_ACT_SCALE * in_scale(p, m0 + row);      // used by the fp16 split only (per pixel row in batch-invariant mode)
     auto load_coefs = [&]() {
         if (HAS_COEF) {
             const size_t co = (size_t)rb * Ct + c_chunk * KC + 8 * kh;
@@ -1070,7 +1081,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void conv_split_rr_kerne
         if (w_tx == 3) { w_tx = 0; ++w_ty; }
         if (w_ty == 3) { w_ty = 0; w_off += w_wrap; }
     };
-    const float xscale = F16_ACT_SCALE * in_scale(p);     // used by the fp16 split only
+    const float xscale = F16_ACT_SCALE * in_scale(p, m0);     // used by the fp16 split only
     auto store_a = [&](int ab) {                          // transform + split + LDS write of the loaded activation registers
         vec pl[NP];
         SP::split(transform<MODE>(areg[0], ca[0], cs[0], aok), transform<MODE>(areg[1], ca[1], cs[1], aok), xscale, pl);
@@ -1123,7 +1134,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void conv_split_rr_kerne
             const int c_begin = min(nch2, split * per), c_end = min(nch2, c_begin + per);
             float s2 = 1.0f;
             {
-                const float b = sqrtf(__uint_as_float(*p.x2_bound));
+                const float b = sqrtf(__uint_as_float(p.x2_bound[bound_index(p, m0)]));
                 if (!(b < 3.0e38f)) s2 = __builtin_nanf("");
                 else if (b > 0.f) s2 = ldexpf(1.0f, 6 - ilogbf(b));
             }
@@ -1176,7 +1187,7 @@ __global__ __launch_bounds__(128 * WM, WM == 2 ? 2 : 1) void conv_split_rr_kerne
                 __syncthreads();
             }
             // both operands into one accumulator: bring the 1x1 partial sums to the 3x3 operand's scale (power of two: exact)
-            const float r = (p.x2_hdr[0] / s2) / (p.w_hdr[0] / in_scale(p));
+            const float r = (p.x2_hdr[0] / s2) / (p.w_hdr[0] / in_scale(p, m0));
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1260,7 +1271,7 @@ __device__ __forceinline__ void wide_epilogue_t(const ConvK& p, f32x16 (&acc)[4]
     const int l31 = lane & 31, half = lane >> 5;
     const int ws_m0 = tail ? p.tail_first * BM : 0;
     const size_t ws_M = tail ? (size_t)p.tail_rows : (size_t)p.M;
-    const float ascale = p.w_hdr[0] / in_scale(p);
+    const float ascale = p.w_hdr[0] / in_scale(p, m0);
     const float oscale = p.out_scale;
     // (the ACT instantiation is the generic one: residual / moments are then run-time conditions)
     const bool has_res = RES && (!ACT || p.res != nullptr), has_stats = STATS && (!ACT || p.stats != nullptr);
@@ -1492,7 +1503,7 @@ __global__ __launch_bounds__(256, 1) void conv_wide_kernel(ConvK p) {
     };
 #endif
 
-    const float xscale = F16_ACT_SCALE * in_scale(p);
+    const float xscale = F16_ACT_SCALE * in_scale(p, m0);
     float4 xr[NU][2], ca[2], cs[2];
     vec a[TM][2];
     auto stage_load = [&](int k, int c) {               // activation registers of staging unit k, chunk c
@@ -1576,7 +1587,7 @@ __global__ __launch_bounds__(256, 1) void conv_wide_kernel(ConvK p) {
         const int c2b = min(nch2, split * per), c2e = min(nch2, c2b + per);
         float s2 = 1.0f;
         {
-            const float bb = sqrtf(__uint_as_float(*p.x2_bound));
+            const float bb = sqrtf(__uint_as_float(p.x2_bound[bound_index(p, m0)]));
             if (!(bb < 3.0e38f)) s2 = __builtin_nanf("");
             else if (bb > 0.f) s2 = ldexpf(1.0f, 6 - ilogbf(bb));
         }
@@ -1678,7 +1689,7 @@ __global__ __launch_bounds__(256, 1) void conv_wide_kernel(ConvK p) {
         }
         __syncthreads();
         // both operands into one accumulator: bring the 1x1 partial sums to the 3x3 operand's scale (power of two: exact)
-        const float r = (p.x2_hdr[0] / s2) / (p.w_hdr[0] / in_scale(p));
+        const float r = (p.x2_hdr[0] / s2) / (p.w_hdr[0] / in_scale(p, m0));
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -2037,7 +2048,7 @@ static int g_force_tm = 0;     // tools/conv_bench.hip (same translation unit) s
 // and the smallest wins.  Checked against measured sweeps on MI355X (tools/conv_bench.hip, mode 2; bf16x6: round 1,
 // DESIGN.md section 3; f16x3: profiles/r02_conv_sweep_f16x3.log and r02_conv_sweep_f16x3_after.log): the pick is the
 // measured optimum or within a few percent of it for the layer shapes of the network at B = 9.
-static void split_tile_cfg(const evc_conv_args* a, long long M, long long ntile, int nsteps, TileCfg& c, bool rr_ok) {
+static void split_tile_cfg(const evc_conv_args* a, long long M, long long ntile, int nsteps, TileCfg& c, bool rr_ok, bool inv) {
     const double K = (double)a->KH * a->KW * (a->C0 + a->C1);
     // Time model of a grid of n equal workgroups of `sps` K-steps each, in units of one workgroup's K-step when it has
     // its CU to itself:  (sps + E) per workgroup (E = prologue + epilogue), x F2 when two share a CU, in rounds of 512
@@ -2055,7 +2066,7 @@ static void split_tile_cfg(const evc_conv_args* a, long long M, long long ntile,
     int best_tm = 2, best_s = 1;
     c.tail_first = 0; c.tail_tiles = 0; c.tail_splits = 1; c.tail_sps = 0;
     for (int tm = 2; tm >= 1; --tm) {
-        if (g_force_tm && tm != g_force_tm) continue;
+        if (!inv && g_force_tm && tm != g_force_tm) continue;
         const long long tiles = ((M + 64 * tm - 1) / (64 * tm)) * ntile;
         const int smax = a->splits > 0 ? a->splits : (nsteps / 4 < 1 ? 1 : (nsteps / 4 > 32 ? 32 : nsteps / 4));
         for (int s = a->splits > 0 ? a->splits : 1; s <= smax; ++s) {
@@ -2080,7 +2091,7 @@ static void split_tile_cfg(const evc_conv_args* a, long long M, long long ntile,
     // then the tiles of the partial round split `ts` ways so that they fill the machine once more with short jobs --
     // instead of splitting EVERY tile (slabs + combine for the whole output) or leaving a mostly idle last round.
     // Same time model (the tail's slabs only cover the tail's rows).
-    if (rr_ok && g_tail_split && a->splits <= 0 && !g_force_tm && M % 128 == 0) {
+    if (!inv && rr_ok && g_tail_split && a->splits <= 0 && !g_force_tm && M % 128 == 0) {
         const long long tm_all = M / 128, wgs = tm_all * ntile;
         const long long R = wgs / 512;
         const long long main_m = R * 512 / ntile, tail_m = tm_all - main_m;
@@ -2117,14 +2128,16 @@ static long long rr_lds_bytes(int np, int bm, int W, int bn) {
 static long long wide_lds_bytes(int W, bool x2) { return (x2 ? 6LL : 4LL) * (256 / W + 2) * (W + 2) * 32; }
 
 // conv_wide_kernel: f16x3, 3x3, 192-channel output tiles, 256-pixel tiles made of whole rows of one image
-static bool wide_ok(const evc_conv_args* a) {
+static bool wide_ok(const evc_conv_args* a, bool inv) {
     const bool mode_ok = a->coef_a ? a->act_in == EVC_ACT_SILU : a->act_in == EVC_ACT_NONE;     // MODE_AFFINE_SILU / MODE_PLAIN
-    return g_wide256 && mode_ok && a->arith == EVC_ARITH_F16X3 && a->KH == 3 && a->KW == 3 && a->Co % 192 == 0 &&
+    return (inv || g_wide256) && mode_ok && a->arith == EVC_ARITH_F16X3 && a->KH == 3 && a->KW == 3 && a->Co % 192 == 0 &&
            (a->W == 16 || a->W == 32 || a->W == 64 || a->W == 128) && ((long long)a->H * a->W) % 256 == 0 &&
            a->ld_out % 4 == 0 && (!a->res || a->ld_res % 4 == 0);      // the epilogue moves 16-byte pieces
 }
 
-static TileCfg conv_tile_cfg(const evc_conv_args* a) {
+// The plan for `a` as given.  `inv`: the caller is planning for batch-invariant mode (conv_tile_cfg below): the process-wide
+// A/B switches are ignored (the plan must be a function of the layer alone), no K-split tail, no 256-pixel row-reuse form.
+static TileCfg conv_tile_cfg_at(const evc_conv_args* a, bool inv) {
     TileCfg c;
     c.wide = 0;
     c.cut_chunk = 0;
@@ -2138,14 +2151,14 @@ static TileCfg conv_tile_cfg(const evc_conv_args* a) {
     if (is_split_arith(a->arith)) {
         const int np = arith_planes(a->arith);
         // row-reuse kernel: 3x3 filters, 128-pixel tiles made of whole image rows (and an LDS image that fits: W >= 4)
-        const bool rr_ok = !g_no_reuse && a->KH == 3 && a->KW == 3 && a->W >= 4 && 128 % a->W == 0 &&
+        const bool rr_ok = (inv || !g_no_reuse) && a->KH == 3 && a->KW == 3 && a->W >= 4 && 128 % a->W == 0 &&
                            rr_lds_bytes(np, 128, a->W, c.bn) <= LDS_CAP;
-        split_tile_cfg(a, M, ntile, nsteps, c, rr_ok);
+        split_tile_cfg(a, M, ntile, nsteps, c, rr_ok, inv);
         if (rr_ok && c.tm == 2) c.reuse = 1;
         // 8-wave / 256-pixel form of the row-reuse kernel (one workgroup per CU = 256 slots).  Measured (B=8, 128x128:
         // exactly 2 rounds) +4-5 %; at B=9 (2.25 rounds) -5 %: the coarser tile makes the tail worse.  So: unsplit
         // grids that are a whole number of >= 2 rounds, or long enough (>= 6 rounds) for the tail not to matter.
-        if (c.reuse && c.splits == 1 && !c.tail_tiles && g_wide_tiles && M % 256 == 0 && rr_lds_bytes(np, 256, a->W, c.bn) <= LDS_CAP) {
+        if (!inv && c.reuse && c.splits == 1 && !c.tail_tiles && g_wide_tiles && M % 256 == 0 && rr_lds_bytes(np, 256, a->W, c.bn) <= LDS_CAP) {
             const long long t256 = (M / 256) * ntile;
             if ((t256 >= 512 && t256 % 256 == 0) || t256 >= 6 * 256) {
                 c.bm = 256;
@@ -2155,7 +2168,7 @@ static TileCfg conv_tile_cfg(const evc_conv_args* a) {
     } else {
         c.tail_first = 0; c.tail_tiles = 0; c.tail_splits = 1; c.tail_sps = 0;
         c.tm = (!EVC_CONV_TM1 || ((M + 127) / 128) * ntile >= 64) ? 2 : 1;
-        if (g_force_tm) c.tm = g_force_tm;
+        if (g_force_tm && !inv) c.tm = g_force_tm;
         c.bm = 64 * c.tm;
         c.tiles = ((M + c.bm - 1) / c.bm) * ntile;
         long long splits = 1;
@@ -2172,7 +2185,7 @@ static TileCfg conv_tile_cfg(const evc_conv_args* a) {
     // Wide kernel (one 256 x 192 workgroup per CU = 256 slots per round): grids that offer at least one full round.  R full
     // rounds of unsplit tiles, then the pixel tiles of the partial round split along K (whole 16-channel chunks, >= 3 per
     // workgroup) so that they fill the machine once more -- the K-split tail of the row-reuse kernel with 256 slots.
-    if (wide_ok(a) && a->splits <= 0 && !g_force_tm) {
+    if (wide_ok(a, inv) && a->splits <= 0 && (inv || !g_force_tm)) {
         const long long tm_all = M / 256, nt = a->Co / 192, wgs = tm_all * nt;
         if (wgs >= 256) {
             const int nchunk = (a->C0 + a->C1) / KC;
@@ -2180,7 +2193,7 @@ static TileCfg conv_tile_cfg(const evc_conv_args* a) {
             c.tail_first = 0; c.tail_tiles = 0; c.tail_splits = 1; c.tail_sps = 0;
             const long long Rr = wgs / 256;
             const long long main_m = Rr * 256 / nt, tail_m = tm_all - main_m;
-            if (g_tail_split && tail_m > 0) {
+            if (!inv && g_tail_split && tail_m > 0) {
                 int ts = (int)(256 / (tail_m * nt));
                 if (ts > nchunk / 3) ts = nchunk / 3;
                 if (ts >= 2) {
@@ -2196,7 +2209,7 @@ static TileCfg conv_tile_cfg(const evc_conv_args* a) {
         // so that tiles x splits fills (at most) one round.  Per workgroup the kernel costs ~23 000 cycles (prologue + epilogue)
         // + ~13 900 per chunk (profiles/r04_wide_stamps_v2.log); an unsplit grid on a little over half of the CUs still beats the
         // 128-pixel tiles split three ways + their combine launch (64x64 192->192: ~95 vs 112 us).  g_wide_mid = 0 disables.
-        if (g_wide_mid && wgs >= 32) {
+        if ((inv || g_wide_mid) && wgs >= 32) {
             const int nchunk = (a->C0 + a->C1) / KC;
             int best_s = 0;
             double best_t = 1e300;
@@ -2216,7 +2229,7 @@ static TileCfg conv_tile_cfg(const evc_conv_args* a) {
                 // 129..255 unsplit workgroups (64 x 64 x 192 channels at B = 9: 144): two UNEQUAL pieces per tile.  The long
                 // pieces start first on `wgs` CUs; the short ones fill the 256 - wgs idle CUs in r = ceil(wgs / (256 - wgs))
                 // turns.  Same cost model: long = 23 000 + 13 900 (nchunk - s), short turns = r (23 000 + 13 900 s), + combine.
-                if (g_wide_cut && best_s == 1 && wgs > 128 && nchunk >= 6) {
+                if ((inv || g_wide_cut) && best_s == 1 && wgs > 128 && nchunk >= 6) {
                     const long long idle = 256 - wgs, r = (wgs + idle - 1) / idle;
                     const double slab_mb = 2.0 * M * a->Co * 4.0 / 1e6;
                     const double comb = 2.0 * 2000.0 * (5.0 + slab_mb / 4.0);
@@ -2242,6 +2255,26 @@ static TileCfg conv_tile_cfg(const evc_conv_args* a) {
     return c;
 }
 
+// BATCH-INVARIANT PLAN (evc_conv_args::invariant).  Everything that shapes an output element's summation tree -- kernel
+// family, tile, split count and boundaries, the unequal cut -- is the default plan of the SAME layer at the reference batch
+// EVC_INVARIANT_REF_BATCH (9: the batch the default plan was tuned at, so the f16x3 3x3 layers at 128x128 / 64x64 / 32x32
+// keep conv_wide_kernel and the measured split of each layer class), without the K-split tail (which pixel tiles a tail
+// splits depends on the number of rounds, i.e. on the sample's row) and with the process-wide A/B switches ignored.  The
+// batch in the arguments only sizes the grid.  Bump EVC_INVARIANT_PLAN_REVISION whenever this, or anything else that changes
+// the bits of invariant mode, changes.
+#define EVC_INVARIANT_PLAN_REVISION 1      // (EVC_INVARIANT_REF_BATCH: include/evc_hip.h)
+static TileCfg conv_tile_cfg(const evc_conv_args* a) {
+    if (!a->invariant) return conv_tile_cfg_at(a, false);
+    evc_conv_args r = *a;
+    r.B = EVC_INVARIANT_REF_BATCH;
+    TileCfg c = conv_tile_cfg_at(&r, true);
+    const long long M = (long long)a->B * a->H * a->W;
+    c.tiles = ((M + c.bm - 1) / c.bm) * (evc_conv_co_pad(a->Co) / c.bn);
+    return c;
+}
+
+extern "C" int evc_invariant_plan_revision(void) { return EVC_INVARIANT_PLAN_REVISION; }
+
 extern "C" int evc_conv_set_option(const char* name, int value) {
     if (!name) return EVC_EINVAL;
     const auto is = [&](const char* s) { int i = 0; while (s[i] && s[i] == name[i]) ++i; return s[i] == 0 && name[i] == 0; };
@@ -2259,6 +2292,8 @@ extern "C" int evc_conv_fused_1x1_supported(const evc_conv_args* a) {
     if (conv_validate(a) != EVC_OK) return 0;
     if (a->arith != EVC_ARITH_F16X3 || a->KH != 3 || a->KW != 3) return 0;
     const TileCfg c = conv_tile_cfg(a);
+    // batch-invariant mode: the fused operand's scale is per sample and tile-uniform in these kernels: whole tiles per sample
+    if (a->invariant && ((long long)a->H * a->W) % c.bm != 0) return 0;
     return (c.reuse == 1 || c.wide) ? 1 : 0;
 }
 
@@ -2292,12 +2327,27 @@ extern "C" int evc_conv_stats_splits(const evc_conv_args* a) {
     if (HW % 64 != 0) return 0;
     const TileCfg c = conv_tile_cfg(a);
     if (c.splits > 1 || c.wide) return HW / 64;                // split-K combine kernel / wide kernel's epilogue: 64-pixel runs
+    // batch-invariant mode: one producer and one run length per layer at every batch.  The epilogue only produces moments
+    // from full tiles, and whether the last tile is full depends on the batch unless tiles are whole fractions of a sample.
+    if (a->invariant && HW % c.bm != 0) return 0;
     // (a K-split tail mixes both producers: the epilogue of the unsplit tiles and the combine of the tail write the same
     // 64-pixel runs, the checks below hold for it because its tiles are full 128-pixel tiles)
     const long long M = (long long)a->B * HW;
     const int CoPad = evc_conv_co_pad(a->Co);
     if (M % c.bm != 0 || a->Co != CoPad || a->Co % c.bn != 0) return 0;
     return HW / (32 * c.tm);                                   // produced by the conv epilogue: one run per wave row
+}
+
+extern "C" int evc_conv_plan_query(const evc_conv_args* a, evc_conv_plan* out) {
+    if (!out || conv_validate(a) != EVC_OK) return EVC_EINVAL;
+    const TileCfg c = conv_tile_cfg(a);
+    if (evc_conv_kernel_name(a, out->kernel, (int)sizeof(out->kernel)) < 0) return EVC_EINVAL;
+    out->tile_m = c.bm; out->tile_n = c.bn; out->splits = c.splits; out->steps_per_split = c.steps_per_split;
+    out->cut_chunk = c.wide ? c.cut_chunk : 0;
+    out->tail_tiles = c.tail_tiles; out->tail_splits = c.tail_tiles ? c.tail_splits : 1;
+    out->stats_runs = evc_conv_stats_splits(a);
+    out->fused_1x1 = evc_conv_fused_1x1_supported(a);
+    return EVC_OK;
 }
 
 extern "C" long long evc_conv_workspace_bytes(const evc_conv_args* a) {
@@ -2474,6 +2524,14 @@ static int conv2d_impl(const evc_conv_args* a, float* ws, void* stream, hipEvent
         k.x2_hdr = a->x2_w_packed;
         k.x2_w = reinterpret_cast<const char*>(a->x2_w_packed) + F16_HDR_BYTES;
         k.x2_bound = a->x2_bound;
+    }
+    k.bound_stride = 0; k.generic_epi = 0;
+    if (a->invariant) {
+        const bool whole = k.HW % cfg.bm == 0;                    // tiles are whole fractions of one sample
+        k.bound_stride = 1;
+        k.generic_epi = whole ? 0 : 1;
+        // the row-reuse / wide kernels take one scale per tile
+        if (!whole && (cfg.reuse || cfg.wide) && (a->in_bound || a->x2_w_packed)) return EVC_EUNSUPPORTED;
     }
     k.tail_first = 0x7fffffff; k.tail_splits = 1; k.tail_sps = 0; k.tail_rows = 0;
     k.cut_chunk = cfg.wide ? cfg.cut_chunk : 0;

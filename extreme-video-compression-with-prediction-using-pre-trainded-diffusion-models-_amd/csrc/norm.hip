@@ -69,6 +69,7 @@ struct CoefArgs {
     unsigned* bound_bits;      // optional: atomicMax of the bit pattern of the largest {sum of squares} entry seen
     unsigned* events;          // optional: sticky range-event word (EVC_RANGE_*), OR-ed, never cleared by a kernel
     unsigned* site_events;     // optional: this call's own word of a per-network site arena (&site_words[site]), OR-ed alike
+    int bound_stride;          // 0: one bound word for the batch; 1: bound_bits[b] (batch-invariant mode)
 };
 
 // fp16-split arithmetic (EVC_ARITH_F16X3) scales GroupNorm-ed operands by 8: they must stay below 65504 / 8
@@ -144,7 +145,8 @@ __global__ __launch_bounds__(256) void gn_coeffs_kernel(CoefArgs a) {
     // consumer's scale becomes NaN and its output with it -- a NaN / inf in the tensor is never turned into finite numbers.
     if (a.bound_bits && tid == 0) {
         const unsigned bits = bad ? NAN_BITS : __float_as_uint(gmx);
-        if (bits > __hip_atomic_load(a.bound_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(a.bound_bits, bits);
+        unsigned* const word = a.bound_bits + b * a.bound_stride;
+        if (bits > __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(word, bits);
     }
     if (bad && tid == 0) raise_event(a.events, a.site_events, EVC_RANGE_NONFINITE);
     sm = red[0][0] + red[0][1] + red[0][2] + red[0][3];
@@ -225,9 +227,9 @@ __global__ __launch_bounds__(256) void gn_coeffs_kernel(CoefArgs a) {
 __global__ __launch_bounds__(256) void moments_bound_kernel(const float* __restrict__ part, int nsplit, int C, int c_begin,
                                                             int c_count, unsigned* __restrict__ bound_bits,
                                                             unsigned* __restrict__ events,
-                                                            unsigned* __restrict__ site_events) {
+                                                            unsigned* __restrict__ site_events, int per_sample) {
     const float* row = part + ((size_t)(blockIdx.y * nsplit + blockIdx.x) * C + c_begin + blockIdx.z * c_count) * 2;
-    bound_bits += blockIdx.z;
+    bound_bits += blockIdx.z + (per_sample ? blockIdx.y * gridDim.z : 0);
     float mx = 0.f;
     unsigned bad = 0;
     for (int i = threadIdx.x; i < c_count; i += 256) {
@@ -350,15 +352,27 @@ extern "C" int evc_gn_coeffs_f32(const float* part0, int nsplit0, int C0, const 
                                    ss_ld, row, coef_a, coef_s, nullptr, nullptr, stream);
 }
 
-extern "C" int evc_moments_bound_site_f32(const float* part, int nsplit, int C, int c_begin, int c_count, int n_ranges,
-                                          int B, unsigned* bound_bits, unsigned* events, unsigned* site_events, int site,
-                                          void* stream) {
+static int moments_bound_impl(const float* part, int nsplit, int C, int c_begin, int c_count, int n_ranges,
+                              int B, unsigned* bound_bits, unsigned* events, unsigned* site_events, int site,
+                              int per_sample, void* stream) {
     if (!part || !bound_bits || nsplit <= 0 || C <= 0 || B <= 0 || c_begin < 0 || c_count <= 0 || n_ranges <= 0 ||
         c_begin + (long long)n_ranges * c_count > C || (site_events && site < 0))
         return EVC_EINVAL;
     hipLaunchKernelGGL(moments_bound_kernel, dim3(nsplit, B, n_ranges), dim3(256), 0, (hipStream_t)stream, part, nsplit, C,
-                       c_begin, c_count, bound_bits, events, site_events ? site_events + site : nullptr);
+                       c_begin, c_count, bound_bits, events, site_events ? site_events + site : nullptr, per_sample);
     return hipGetLastError() == hipSuccess ? EVC_OK : EVC_ELAUNCH;
+}
+
+extern "C" int evc_moments_bound_site_f32(const float* part, int nsplit, int C, int c_begin, int c_count, int n_ranges,
+                                          int B, unsigned* bound_bits, unsigned* events, unsigned* site_events, int site,
+                                          void* stream) {
+    return moments_bound_impl(part, nsplit, C, c_begin, c_count, n_ranges, B, bound_bits, events, site_events, site, 0, stream);
+}
+
+extern "C" int evc_moments_bound_sample_f32(const float* part, int nsplit, int C, int c_begin, int c_count, int n_ranges,
+                                            int B, unsigned* bound_bits, unsigned* events, unsigned* site_events, int site,
+                                            void* stream) {
+    return moments_bound_impl(part, nsplit, C, c_begin, c_count, n_ranges, B, bound_bits, events, site_events, site, 1, stream);
 }
 
 extern "C" int evc_moments_bound_f32(const float* part, int nsplit, int C, int c_begin, int c_count, int n_ranges, int B,
@@ -367,20 +381,38 @@ extern "C" int evc_moments_bound_f32(const float* part, int nsplit, int C, int c
                                       stream);
 }
 
-extern "C" int evc_gn_coeffs_bound_site_f32(const float* part0, int nsplit0, int C0, const float* part1, int nsplit1,
-                                            int C1, int B, int HW, int groups, float eps, int mode, const float* gamma,
-                                            const float* beta, const float* ss, int ss_ld, const int* row, float* coef_a,
-                                            float* coef_s, unsigned* bound_bits, unsigned* events, unsigned* site_events,
-                                            int site, void* stream) {
+static int gn_coeffs_impl(const float* part0, int nsplit0, int C0, const float* part1, int nsplit1,
+                          int C1, int B, int HW, int groups, float eps, int mode, const float* gamma,
+                          const float* beta, const float* ss, int ss_ld, const int* row, float* coef_a,
+                          float* coef_s, unsigned* bound_bits, unsigned* events, unsigned* site_events,
+                          int site, int per_sample, void* stream) {
     if (!part0 || C0 <= 0 || nsplit0 <= 0 || C1 < 0 || (C1 > 0 && (!part1 || nsplit1 <= 0))) return EVC_EINVAL;
     if (B <= 0 || HW <= 0 || groups <= 0 || (C0 + C1) % groups != 0 || !coef_a || !coef_s) return EVC_EINVAL;
     if (mode < 0 || mode > 2 || (mode == 1 && (!gamma || !beta)) || (mode == 2 && (!ss || ss_ld < 2 * (C0 + C1))))
         return EVC_EINVAL;
     if (site_events && site < 0) return EVC_EINVAL;
     CoefArgs a{part0, nsplit0, C0, part1, nsplit1, C1, B, HW, groups, eps, mode, gamma, beta, ss, ss_ld, row,
-               coef_a, coef_s, bound_bits, events, site_events ? site_events + site : nullptr};
+               coef_a, coef_s, bound_bits, events, site_events ? site_events + site : nullptr, per_sample};
     hipLaunchKernelGGL(gn_coeffs_kernel, dim3(groups, B), dim3(256), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? EVC_OK : EVC_ELAUNCH;
+}
+
+extern "C" int evc_gn_coeffs_bound_site_f32(const float* part0, int nsplit0, int C0, const float* part1, int nsplit1,
+                                            int C1, int B, int HW, int groups, float eps, int mode, const float* gamma,
+                                            const float* beta, const float* ss, int ss_ld, const int* row, float* coef_a,
+                                            float* coef_s, unsigned* bound_bits, unsigned* events, unsigned* site_events,
+                                            int site, void* stream) {
+    return gn_coeffs_impl(part0, nsplit0, C0, part1, nsplit1, C1, B, HW, groups, eps, mode, gamma, beta, ss, ss_ld, row,
+                          coef_a, coef_s, bound_bits, events, site_events, site, 0, stream);
+}
+
+extern "C" int evc_gn_coeffs_bound_sample_f32(const float* part0, int nsplit0, int C0, const float* part1, int nsplit1,
+                                              int C1, int B, int HW, int groups, float eps, int mode, const float* gamma,
+                                              const float* beta, const float* ss, int ss_ld, const int* row, float* coef_a,
+                                              float* coef_s, unsigned* bound_bits, unsigned* events, unsigned* site_events,
+                                              int site, void* stream) {
+    return gn_coeffs_impl(part0, nsplit0, C0, part1, nsplit1, C1, B, HW, groups, eps, mode, gamma, beta, ss, ss_ld, row,
+                          coef_a, coef_s, bound_bits, events, site_events, site, 1, stream);
 }
 
 extern "C" int evc_gn_coeffs_bound_f32(const float* part0, int nsplit0, int C0, const float* part1, int nsplit1, int C1,

@@ -26,8 +26,12 @@ def all_generated_mask(frames=30, key=2, chunk=5):
 
 
 class ClipDecoder:
-    def __init__(self, scorenet, elic_model, config, sampler, groups=1, range_recovery=None, log=print):
+    def __init__(self, scorenet, elic_model, config, sampler, groups=1, range_recovery=None, log=print, batch_invariant=False):
         self.net, self.elic, self.config, self.sampler = scorenet, elic_model, config, sampler
+        # batch_invariant: ``generate`` runs on the network's batch-invariant view by default (a sample's frames then do not
+        # depend on the launch it rides in); ``generate(..., invariant=)`` / format-4 jobs of ``decode_jobs`` choose per call
+        self.batch_invariant = bool(batch_invariant)
+        self._inv_net = None
         self.device = scorenet.device
         self.groups = groups          # concurrent clip groups (HIP streams) during generation
         self._stream_pool = []
@@ -35,6 +39,9 @@ class ClipDecoder:
         # the event demoted to the bf16 split (recovery.py); "off" (default, or EVC_RANGE_RECOVERY): the caller's
         # check_numerics stops the run.  Networks without event sites (UNetDDPM, pseudo-3-D) keep the "off" behaviour.
         self.range_recovery = recovery_mode(range_recovery)
+        if self.batch_invariant:
+            self._refuse_recovery()
+            self.invariant_net()           # fail now for a network without the mode
         self.log = log
         self.chunks = 0               # generated chunks so far (recovery log lines name them)
         self.recovery_passes = []     # passes of every chunk recovery regenerated
@@ -42,8 +49,25 @@ class ClipDecoder:
     def recovers(self):
         return self.range_recovery == "layer" and supports_recovery(self.net)
 
+    def _refuse_recovery(self):
+        if self.range_recovery == "layer":
+            raise ValueError("batch-invariant generation does not combine with range recovery (range_recovery='layer'): one "
+                             "sample's event would demote layers for every sample and for the rest of the run, and a "
+                             "receiver could not know which")
+
+    def invariant_net(self):
+        """The batch-invariant view of the score network (shares its packed weights), built on first use."""
+        if self._inv_net is None:
+            if getattr(self.net, "batch_invariant", False):
+                self._inv_net = self.net
+            elif hasattr(self.net, "invariant_view"):
+                self._inv_net = self.net.invariant_view()
+            else:
+                raise NotImplementedError(f"batch-invariant generation is not built for {type(self.net).__name__}")
+        return self._inv_net
+
     @torch.no_grad()
-    def generate(self, cond_frames, noise_fn=None, generator=None, groups=None):
+    def generate(self, cond_frames, noise_fn=None, generator=None, groups=None, invariant=None):
         """cond_frames: (B, 2, 3, H, W) in [0, 1] on the device -> (B, 5, 3, H, W) in [0, 1].
         = SenderCity.generate_frame (city_sender.py:326-351) without the per-chunk checkpoint reload.
 
@@ -58,6 +82,10 @@ class ClipDecoder:
         seeds from the host entropy pool and replay with new noise), and the network's ``cond_generator``; ``noise_fn``
         must be deterministic (the policy sweep's counter-based noise is)."""
         self.chunks += 1
+        invariant = self.batch_invariant if invariant is None else bool(invariant)
+        if invariant:
+            self._refuse_recovery()
+            return self._generate(cond_frames, noise_fn, generator, groups, net=self.invariant_net())
         if not self.recovers():
             return self._generate(cond_frames, noise_fn, generator, groups)
         net = self.net
@@ -85,13 +113,14 @@ class ClipDecoder:
             self.recovery_passes.append(passes)
         return res["frames"]
 
-    def _generate(self, cond_frames, noise_fn, generator, groups, with_raw=False):
+    def _generate(self, cond_frames, noise_fn, generator, groups, with_raw=False, net=None):
         from . import sampler as S
         cfg = self.config
+        net = self.net if net is None else net
         B, _, C, H, W = cond_frames.shape
         groups = self.groups if groups is None else groups
         groups = max(1, min(int(groups), B))
-        if getattr(self.net, "SPADE", False):
+        if getattr(net, "SPADE", False):
             # the SPADE network caches its per-chunk gamma / beta maps for ONE conditioning tensor: interleaved clip groups
             # would each pass their own slice and rebuild all maps on every forward (~20 ms against a 15 ms forward)
             groups = 1
@@ -112,16 +141,16 @@ class ClipDecoder:
         if groups == 1 or step_gen is None:
             x_T = draw("init", 0, B, generator)
             step_noise = None if noise_fn is None else (lambda i, x: draw(i, 0, B, None))
-            out = self.sampler(x_T, self.net, cond=cond, noise_fn=step_noise, generator=generator, **kw)
+            out = self.sampler(x_T, net, cond=cond, noise_fn=step_noise, generator=generator, **kw)
             pred = out[-1].contiguous()
         else:
             bounds = [(g * B // groups, (g + 1) * B // groups) for g in range(groups)]
             main = torch.cuda.current_stream()
             streams = self._streams(groups)
-            if hasattr(self.net, "prepare_labels"):
+            if hasattr(net, "prepare_labels"):
                 # AdaGN table rows are shared state: build every row this sampler will read (F-PNDM: incl. the
                 # Runge-Kutta midpoints and -1) on the main stream, which all group streams wait on below
-                self.net.prepare_labels(S.label_set(self.sampler, self.net, kw["subsample_steps"], kw["denoise"]))
+                net.prepare_labels(S.label_set(self.sampler, net, kw["subsample_steps"], kw["denoise"]))
             gens = []
             for (lo, hi), st in zip(bounds, streams):
                 st.wait_stream(main)
@@ -133,7 +162,7 @@ class ClipDecoder:
                                           if generator is not None else torch.seed() % (2 ** 31))
                     x_T = draw("init", lo, hi, gen_g)
                     sn = None if noise_fn is None else (lambda i, x, lo=lo, hi=hi: draw(i, lo, hi, None))
-                    gens.append(step_gen(x_T, self.net, cond=cond[lo:hi].contiguous(), noise_fn=sn, generator=gen_g, **kw))
+                    gens.append(step_gen(x_T, net, cond=cond[lo:hi].contiguous(), noise_fn=sn, generator=gen_g, **kw))
             outs = S.run_interleaved(gens, streams)
             for st in streams:
                 main.wait_stream(st)
@@ -196,7 +225,9 @@ class ClipDecoder:
         frames; a segment is never split).  ``models``: q -> ElicModel (default: this decoder's own model for every q);
         ``size`` = (H, W) of a frame (default: the generator's image size): the ELIC output is cropped to it, as the sender
         crops its padded frames.  The generator settings of the streams (sampler, subsample steps, denoise) must be the ones
-        this decoder was built with.  Returns one (frames, 3, H, W) float32 device tensor per job."""
+        this decoder was built with.  Format-4 jobs (``job["plan"]`` set: generated in batch-invariant mode) run their
+        generation rounds on the network's batch-invariant view, in launches of their own: their frames are the sender's
+        bit for bit at any ``max_batch``.  Returns one (frames, 3, H, W) float32 device tensor per job."""
         from . import container as Cn, sampler as S
         cfg = self.config
         mine = (getattr(cfg.sampling, "subsample", None) or 0, bool(cfg.sampling.denoise))
@@ -219,13 +250,14 @@ class ClipDecoder:
                 break
             gen = [i for i in todo if jobs[i]["segments"][pos[i]][0] == "gen"]
             key = [i for i in todo if jobs[i]["segments"][pos[i]][0] == "key"]
-            for seed in sorted({jobs[i]["seed"] for i in gen}):          # one seed per noise launch
-                same = [i for i in gen if jobs[i]["seed"] == seed]
+            # one seed per noise launch, one generation plan per score-network launch
+            for seed, inv in sorted({(jobs[i]["seed"], jobs[i].get("plan") is not None) for i in gen}):
+                same = [i for i in gen if jobs[i]["seed"] == seed and (jobs[i].get("plan") is not None) == inv]
                 for c0 in range(0, len(same), max_batch):
                     part = same[c0:c0 + max_batch]
                     cond = torch.stack([torch.stack(x[i][-2:], 0) for i in part], 0).contiguous()
                     keys = L.noise_keys([(jobs[i]["stream_id"], len(x[i])) for i in part], self.device)
-                    pred = self.generate(cond, groups=1, noise_fn=lambda tag, shape, keys=keys, seed=seed: L.noise_normal(
+                    pred = self.generate(cond, groups=1, invariant=inv, noise_fn=lambda tag, shape, keys=keys, seed=seed: L.noise_normal(
                         keys, shape, seed, 0 if tag == "init" else int(tag) + 1))
                     assert pred.shape[1] * pred.shape[2] == ch
                     for k, i in enumerate(part):

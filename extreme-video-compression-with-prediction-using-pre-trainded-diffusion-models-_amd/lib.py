@@ -68,7 +68,14 @@ class ConvArgs(ctypes.Structure):
                 ("B", c_int), ("H", c_int), ("W", c_int), ("Co", c_int), ("KH", c_int), ("KW", c_int),
                 ("splits", c_int), ("stats_out", c_void_p), ("arith", c_int), ("in_bound", c_void_p),
                 ("x2_src0", c_void_p), ("x2_src1", c_void_p), ("x2_C0", c_int), ("x2_C1", c_int), ("x2_ld0", c_int),
-                ("x2_ld1", c_int), ("x2_w_packed", c_void_p), ("x2_bound", c_void_p)]
+                ("x2_ld1", c_int), ("x2_w_packed", c_void_p), ("x2_bound", c_void_p), ("invariant", c_int)]
+
+
+class ConvPlan(ctypes.Structure):
+    """Mirror of ``evc_conv_plan`` (include/evc_hip.h): what ``evc_conv_plan_query`` reports."""
+    _fields_ = [("kernel", ctypes.c_char * 96), ("tile_m", c_int), ("tile_n", c_int), ("splits", c_int),
+                ("steps_per_split", c_int), ("cut_chunk", c_int), ("tail_tiles", c_int), ("tail_splits", c_int),
+                ("stats_runs", c_int), ("fused_1x1", c_int)]
 
 
 # name -> (restype, argtypes); exactly the symbols declared in include/evc_hip.h
@@ -105,6 +112,16 @@ HIP_SYMBOLS = {
                                              c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "evc_moments_bound_site_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                            c_int, c_void_p]),
+    "evc_invariant_plan_revision": (c_int, []),
+    "evc_conv_plan_query": (c_int, [POINTER(ConvArgs), POINTER(ConvPlan)]),
+    "evc_gn_coeffs_bound_sample_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                               c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "evc_moments_bound_sample_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_int, c_void_p]),
+    "evc_attention_invariant_workspace_bytes": (c_longlong, [c_int, c_int, c_int, c_int]),
+    "evc_attention_invariant_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                            c_float, c_void_p, c_void_p, c_void_p]),
     "evc_attention_f16x3_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                         c_float, c_void_p, c_void_p, c_void_p]),
     "evc_deconv5x5s2_phase_weights_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
@@ -298,18 +315,26 @@ def nhwc_to_nchw(x, C, out=None):
     return out
 
 
-def stats_splits(B, HW):
+# ---- batch-invariant mode (include/evc_hip.h) ---------------------------------------------------------------------
+# Every wrapper below that plans by batch takes ``invariant=``: True asks the library for the batch-invariant plan of that
+# call.  Per call, here as in the C ABI: there is no process-wide or ambient switch, a caller passes the flag on every call
+# (``ScoreNet`` does through its ``_conv`` / ``_gn`` / ... helpers).
+def invariant_plan_revision():
+    """Integer bumped whenever a change alters the bits of batch-invariant mode (job streams carry it)."""
+    return int(hip_lib(require_device=False).evc_invariant_plan_revision())
+
+
+def stats_splits(B, HW, invariant=False):
     """Number of pixel ranges per image for evc_chan_stats_f32: enough blocks to fill the chip while every
-    block still streams >= 64 pixels."""
-    n = max(1, min(HW // 64, (1024 + B - 1) // B))
-    return n
+    block still streams >= 64 pixels; ``invariant``: from HW only."""
+    return max(1, min(HW // 64, 128 if invariant else (1024 + B - 1) // B))
 
 
-def chan_stats(x):
-    """x: (B, H, W, C) -> partial moments (B, nsplit, C, 2)."""
+def chan_stats(x, invariant=False):
+    """x: (B, H, W, C) -> partial moments (B, nsplit, C, 2).  ``invariant``: pixel ranges from H*W only."""
     L = hip_lib()
     B, H, W, C = x.shape
-    ns = stats_splits(B, H * W)
+    ns = stats_splits(B, H * W, bool(invariant))
     part = torch.empty((B, ns, C, 2), device=x.device, dtype=torch.float32)
     _check(L.evc_chan_stats_f32(fptr(x), fptr(part), B, H * W, C, ns, stream_ptr()), "evc_chan_stats_f32")
     return part
@@ -495,7 +520,8 @@ def gpu_power_w(device=None):
     return None
 
 
-def gn_coeffs(parts, HW, groups, eps, mode=0, gamma=None, beta=None, ss=None, row=None, bound=None, site=None):
+def gn_coeffs(parts, HW, groups, eps, mode=0, gamma=None, beta=None, ss=None, row=None, bound=None, site=None,
+              invariant=False):
     """parts: one or two partial-moment tensors (virtual concat). Returns (coef_a, coef_s), each (B, C).
     ``bound``: optional one-element int32 tensor (zeroed by the caller) raised to the bit pattern of the tensors'
     element bound S (|x| <= sqrt(S)) -- what ``conv2d_nhwc(..., in_bound=)`` takes.  ``site``: a ``Site`` that also
@@ -510,6 +536,13 @@ def gn_coeffs(parts, HW, groups, eps, mode=0, gamma=None, beta=None, ss=None, ro
     cs = torch.empty((B, C), device=p0.device, dtype=torch.float32)
     ss_ld = 0 if ss is None else ss.stride(0)
     ssp = c_void_p(ss.data_ptr()) if ss is not None else None
+    if bool(invariant) and bound is not None:        # one bound word per sample
+        ev, sw, si = _site_args(site, p0.device)
+        _check(L.evc_gn_coeffs_bound_sample_f32(fptr(p0), ns0, C0, fptr(p1), ns1, C1, B, HW, groups, eps, mode, fptr(gamma),
+                                                fptr(beta), ssp, ss_ld, fptr(row, torch.int32), fptr(ca), fptr(cs),
+                                                _word(bound, B), ev, sw, si, stream_ptr()),
+               "evc_gn_coeffs_bound_sample_f32")
+        return ca, cs
     if site is None:
         _check(L.evc_gn_coeffs_bound_f32(fptr(p0), ns0, C0, fptr(p1), ns1, C1, B, HW, groups, eps, mode, fptr(gamma),
                                          fptr(beta), ssp, ss_ld, fptr(row, torch.int32), fptr(ca), fptr(cs), _word(bound),
@@ -531,11 +564,17 @@ def _word(t, n=1):
     return c_void_p(t.data_ptr())
 
 
-def moments_bound(part, c_begin, c_count, bound, site=None):
+def moments_bound(part, c_begin, c_count, bound, site=None, invariant=False):
     """Raise ``bound[z]`` to the element bound of channels [c_begin + z*c_count, + c_count) of a moments tensor
     (B, ns, C, 2), for z < bound.numel().  ``site``: as in ``gn_coeffs``."""
     B, ns, C, _ = part.shape
     n = bound.numel()
+    if bool(invariant):                              # bound: (B, n_ranges) words, sample-major
+        assert n % B == 0
+        ev, sw, si = _site_args(site, part.device)
+        _check(hip_lib().evc_moments_bound_sample_f32(fptr(part), ns, C, c_begin, c_count, n // B, B, _word(bound, n),
+                                                      ev, sw, si, stream_ptr()), "evc_moments_bound_sample_f32")
+        return
     if site is not None:
         _check(hip_lib().evc_moments_bound_site_f32(fptr(part), ns, C, c_begin, c_count, n, B, _word(bound, n),
                                                     *_site_args(site, part.device), stream_ptr()),
@@ -662,24 +701,46 @@ def _src(s):
     return ptr(s), s.shape[-1], s.shape[-1], s.shape[:3]
 
 
-def conv_fused_1x1_supported(B, H, W, Ci, Co, arith, splits=0):
+def conv_fused_1x1_supported(B, H, W, Ci, Co, arith, splits=0, invariant=False):
     """Whether a 3x3 convolution of this shape may carry a fused 1x1 operand (``conv2d_nhwc(..., x2=)``): C query.  It
     needs the f16x3 row-reuse kernel, i.e. 128-pixel tiles: very small grids, for which 64-pixel tiles are chosen, do not."""
     d = c_void_p(16)
     a = ConvArgs(d, None, Ci, 0, 0, 0, None, None, ACT_NONE, d, None, None, 0, 1.0, ACT_NONE, d, Co, B, H, W, Co, 3, 3, splits,
                  None, arith, None)
+    a.invariant = int(bool(invariant))
     return bool(hip_lib(require_device=False).evc_conv_fused_1x1_supported(ctypes.byref(a)))
 
 
+def conv_plan(B, H, W, C0, C1, Co, K, arith, coef=False, act_in=ACT_NONE, x2_ci=0, invariant=False, splits=0):
+    """The whole plan of a convolution without a launch (``evc_conv_plan_query``; works without a GPU): a dict of the kernel
+    instance, tile, K split (count, steps per split, cut), K-split tail, fused-moment runs and whether a fused 1x1 operand
+    is accepted.  ``coef`` / ``act_in``: the on-load mode (GroupNorm coefficients, activation); ``x2_ci``: channels of a
+    fused 1x1 operand (f16x3 only)."""
+    d = c_void_p(16)      # any non-null pointers: the query reads shapes only
+    a = ConvArgs(d, d if C1 else None, C0, C1, 0, 0, d if coef else None, d if coef else None, act_in, d, None, None, 0, 1.0,
+                 ACT_NONE, d, Co, B, H, W, Co, K, K, splits, None, arith, None)
+    if x2_ci:
+        a.x2_src0, a.x2_C0, a.x2_w_packed, a.x2_bound = d, x2_ci, d, d
+    a.invariant = int(bool(invariant))
+    out = ConvPlan()
+    _check(hip_lib(require_device=False).evc_conv_plan_query(ctypes.byref(a), ctypes.byref(out)), "evc_conv_plan_query")
+    return dict(kernel=out.kernel.decode(), tile=(out.tile_m, out.tile_n), splits=out.splits,
+                steps_per_split=out.steps_per_split, cut_chunk=out.cut_chunk, tail_tiles=out.tail_tiles,
+                tail_splits=out.tail_splits, stats_runs=out.stats_runs, fused_1x1=bool(out.fused_1x1))
+
+
 def conv2d_nhwc(src0, w_packed, Co, KH, KW, bias=None, src1=None, coef=None, act_in=ACT_NONE, res=None,
-                out_scale=1.0, act_out=ACT_NONE, out=None, splits=0, want_stats=False, in_bound=None, x2=None):
+                out_scale=1.0, act_out=ACT_NONE, out=None, splits=0, want_stats=False, in_bound=None, x2=None,
+                invariant=False):
     """out = act_out((conv(act_in(cat[src0,src1]*a+s), w) + bias + res) * out_scale); tensors are NHWC.
     ``src0`` / ``src1`` / ``out`` may be ``Cols`` channel slices of wider tensors.
     ``x2 = (x2_src0, x2_src1 or None, w2_packed, bound)``: a fused 1x1 operand -- conv1x1(cat[x2_src0, x2_src1], w2) is
     accumulated into the same output (include/evc_hip.h); ``bias`` must then be the sum of both convolutions' biases.
     ``want_stats=True`` returns ``(out, stats)``: per-channel moments of ``out`` in ``chan_stats`` layout, produced
-    by the conv epilogue when the shape allows it, else by a separate ``evc_chan_stats_f32`` pass."""
+    by the conv epilogue when the shape allows it, else by a separate ``evc_chan_stats_f32`` pass.
+    ``invariant``: the batch-invariant plan; ``in_bound`` / the bound of ``x2`` then hold one word per sample."""
     L = hip_lib()
+    inv = bool(invariant)
     p0, C0, ld0, shp = _src(src0)
     p1, C1, ld1, shp1 = _src(src1)
     assert shp1 is None or tuple(shp1) == tuple(shp)
@@ -692,14 +753,15 @@ def conv2d_nhwc(src0, w_packed, Co, KH, KW, bias=None, src1=None, coef=None, act
     ca, cs = coef if coef is not None else (None, None)
     a = ConvArgs(p0, p1, C0, C1, ld0, ld1, ptr(ca), ptr(cs), act_in, ptr(w_packed), ptr(bias), ptr(res),
                  0 if res is None else res.shape[-1], float(out_scale), act_out, po, ldo,
-                 B, H, W, Co, KH, KW, splits, None, packed_arith(w_packed), _word(in_bound))
+                 B, H, W, Co, KH, KW, splits, None, packed_arith(w_packed), _word(in_bound, B if inv else 1))
+    a.invariant = int(inv)
     x2_ci = 0
     if x2 is not None:
         q0, qC0, qld0, qshp = _src(x2[0])
         q1, qC1, qld1, _ = _src(x2[1])
         assert tuple(qshp) == (B, H, W) and x2[2].dtype == torch.float16
         a.x2_src0, a.x2_src1, a.x2_C0, a.x2_C1, a.x2_ld0, a.x2_ld1 = q0, q1, qC0, qC1, qld0, qld1
-        a.x2_w_packed, a.x2_bound = ptr(x2[2]), _word(x2[3])
+        a.x2_w_packed, a.x2_bound = ptr(x2[2]), _word(x2[3], B if inv else 1)
         x2_ci = qC0 + qC1
     stats = None
     if want_stats:
@@ -728,12 +790,12 @@ def conv2d_nhwc(src0, w_packed, Co, KH, KW, bias=None, src1=None, coef=None, act
                                  call=dict(B=B, H=H, W=W, C0=C0, C1=C1, Co=Co, K=KH, coef=coef is not None, act_in=act_in,
                                            res=res is not None, out_scale=float(out_scale), bias=bias is not None,
                                            bound=in_bound is not None, arith=a.arith, ld_out=ldo,
-                                           stats=bool(want_stats), x2=x2_ci)))
+                                           stats=bool(want_stats), x2=x2_ci, invariant=inv)))
     else:
         _check(L.evc_conv2d_nhwc_f32(ctypes.byref(a), ptr(ws), stream_ptr()), "evc_conv2d_nhwc_f32")
     result = out.t if isinstance(out, Cols) else out
     if want_stats:
-        return result, (stats if stats is not None else chan_stats(result))
+        return result, (stats if stats is not None else chan_stats(result, invariant=inv))
     return result
 
 
@@ -761,7 +823,7 @@ def attention_set_option(name, value):
         raise EvcKernelError(f"unknown attention option {name!r}")
 
 
-def attention(qkv, C, heads, out=None, bounds=None):
+def attention(qkv, C, heads, out=None, bounds=None, invariant=False):
     """qkv: (B, N, 3C) with q | k | v concatenated along channels; returns (B, N, C).  ``bounds``: three int32 words
     (element bounds of q, k, v from ``moments_bound``) select the fp16-split kernel; None the f32-MFMA one."""
     L = hip_lib()
@@ -770,6 +832,14 @@ def attention(qkv, C, heads, out=None, bounds=None):
     if out is None:
         out = torch.empty((B, N, C), device=qkv.device, dtype=torch.float32)
     base = qkv.data_ptr()
+    if bool(invariant):      # plan from (heads, N, D) only; bounds: (B, 3) words
+        nbytes = L.evc_attention_invariant_workspace_bytes(B, heads, N, D)
+        ws = _workspace(nbytes, qkv.device) if nbytes > 0 else None
+        _check(L.evc_attention_invariant_f32(c_void_p(base), c_void_p(base + 4 * C), c_void_p(base + 8 * C), ld, fptr(out), C,
+                                             B, heads, N, D, float(int(D) ** (-0.5)),
+                                             None if bounds is None else _word(bounds, 3 * B), ptr(ws), stream_ptr()),
+               "evc_attention_invariant_f32")
+        return out
     nbytes = L.evc_attention_workspace_bytes(B, heads, N, D)
     ws = _workspace(nbytes, qkv.device) if nbytes > 0 else None      # stream-ordered: shared with the conv workspace
     if bounds is not None:

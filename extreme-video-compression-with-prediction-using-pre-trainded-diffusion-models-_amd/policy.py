@@ -134,7 +134,7 @@ class _Job:
 
 
 def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=30, max_batch=32, seed=0,
-               bpp_limit=1.0, device="cuda", log=None, noise_source=None, stats=None, noise="torch"):
+               bpp_limit=1.0, device="cuda", log=None, noise_source=None, stats=None, noise="torch", batch_invariant=False):
     """The reference's sweep, batched.
 
     decoder:       ClipDecoder (only ``generate`` is used: the generator does not depend on q)
@@ -147,6 +147,9 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
                    (DESIGN.md section 5), one ``evc_noise_normal_f32`` launch per step keyed by (seed, stream id = the job's
                    number, start frame = frames the job holds when the round starts, step).  Only "evc" can be replayed
                    by a receiver (container.pack_job / ClipDecoder.decode_jobs); ``noise_source`` wins over both
+    batch_invariant: generate on the score network's batch-invariant view: a job's frames then do not
+                   depend on the launches it rode in, so a receiver reproduces them bit for bit at any batch size
+                   (container format 4).  Needs noise="evc", as job streams do; every result then carries ``invariant=True``
     stats:         optional dict, filled with the launch-size histogram {batch size: generation launches}, the number of
                    generation rounds and of key frames coded, and the host seconds spent drawing noise
     Returns {(vid, q): [dict(thr, x (frames,3,H,W) float32 numpy, d (frames,) int, bits [..], bpp, segments, stream_id,
@@ -157,6 +160,11 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
     key is never reused, because the fall-back moves the start frame on); ``key_strings`` the key frames' strings in order."""
     if noise not in ("torch", "evc"):
         raise ValueError(f"noise must be 'torch' or 'evc', not {noise!r}")
+    if batch_invariant and noise != "evc":
+        raise ValueError("batch_invariant needs noise='evc': torch's generators are not replayable by a receiver, so there is "
+                         "nobody to reproduce the frames")
+    if batch_invariant:
+        decoder._refuse_recovery()
     if noise == "evc" and noise_source is None:
         cfg = decoder.config
         if getattr(cfg.model, "gamma", False):
@@ -236,7 +244,8 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
         for c0 in range(0, len(active), max_batch):
             batch = active[c0:c0 + max_batch]
             cond = torch.stack([torch.stack(j.x[-2:], 0) for j in batch], 0).contiguous()     # (n, 2, 3, H, W)
-            pred = decoder.generate(cond, noise_fn=noise_for(batch), groups=1)              # (n, 5, 3, H, W)
+            pred = decoder.generate(cond, noise_fn=noise_for(batch), groups=1,              # (n, 5, 3, H, W)
+                                    invariant=True if batch_invariant else None)
             if stats is not None:
                 h = stats.setdefault("launch_sizes", {})
                 h[len(batch)] = h.get(len(batch), 0) + 1
@@ -278,7 +287,7 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
             continue
         lst.append(dict(thr=j.thr, x=torch.stack(j.x[:frames], 0).cpu().numpy(), d=np.asarray(j.d[:frames], dtype=np.int64),
                         bits=list(j.bits), bpp=bpp, segments=list(j.segments), stream_id=j.uid, seed=int(seed),
-                        key_strings=list(j.strings), shape=shapes[0]))
+                        key_strings=list(j.strings), shape=shapes[0], invariant=bool(batch_invariant)))
     return {k: [r for r in v if r is not None] for k, v in out.items()}
 
 

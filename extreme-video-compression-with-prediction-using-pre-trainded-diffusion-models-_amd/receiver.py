@@ -1,5 +1,8 @@
 """Receiver for policy-coded clips: decodes the job streams a ``city_sender.py --policy psnr|lpips --bitstream-dir DIR`` run
-wrote (container format 3, one file per reported (video, q, threshold) job) with nothing but the model files.
+wrote (container format 3, or 4 for jobs generated with ``--batch-invariant``; one file per reported (video, q, threshold)
+job) with nothing but the model files.  A format-4 job is decoded on the score network's batch-invariant view, whatever
+``--batch`` is; the CRC-32 of its frames is compared with the sender's and ``frames: match`` / ``frames: MISMATCH`` printed
+per job (any mismatch makes the exit status non-zero).
 
     python city_receiver.py --bitstream-dir DIR --output_path OUT [--config ... --exp ... --ckpt ... -p ... | --synthetic]
 
@@ -27,9 +30,13 @@ def write_job_streams(directory, results, models, sampler, cfg):
     paths = {}
     for (vid, q), lst in results.items():
         for r in lst:
+            extra = {}
+            if r.get("invariant"):       # format 4: the plan the frames were generated under, and their checksum
+                from . import lib as L
+                extra = dict(plan=(container.PLAN_INVARIANT, L.invariant_plan_revision()), crc=container.frames_crc(r["x"]))
             blob = container.pack_job(r["segments"], r["key_strings"], r["shape"], models[q].codec_tag(), r["seed"],
                                       r["stream_id"], vid, q, r["thr"], sampler, getattr(cfg.sampling, "subsample", None) or 0,
-                                      cfg.sampling.denoise)
+                                      cfg.sampling.denoise, **extra)
             path = os.path.join(directory, container.job_file_name(vid, q, r["thr"]))
             with open(path, "wb") as fh:
                 fh.write(blob)
@@ -50,11 +57,16 @@ def decode_streams(blobs, net, cfg, model_for, max_batch=32, range_recovery=None
     """blobs: [bytes]; model_for: q -> ElicModel (called once per q the streams name); -> ([job dict], [frames tensor]) in
     the order given.  A stream coded under another entropy arithmetic raises ``container.CodecMismatch``."""
     import copy
-    from . import sampler as S
+    from . import lib as L, sampler as S
     from .decoder import ClipDecoder
-    jobs = [container.unpack_job(b) for b in blobs]
+    rev = L.invariant_plan_revision()
+    jobs = [container.unpack_job(b, expect_plan_revision=rev) for b in blobs]
+    if recovery_is_layer(range_recovery) and any(j["plan"] is not None for j in jobs):
+        raise ValueError("format-4 job streams (batch-invariant generation) do not combine with range recovery "
+                         "(--range-recovery layer)")
     models = {q: model_for(q) for q in sorted({j["q"] for j in jobs})}
-    jobs = [container.unpack_job(b, expect_codec=models[j["q"]].codec_tag()) for b, j in zip(blobs, jobs)]
+    jobs = [container.unpack_job(b, expect_codec=models[j["q"]].codec_tag(), expect_plan_revision=rev)
+            for b, j in zip(blobs, jobs)]
     frames = [None] * len(jobs)
     decoders = []
     for setting in sorted({(j["sampler"], j["subsample"], j["denoise"]) for j in jobs}):
@@ -67,6 +79,18 @@ def decode_streams(blobs, net, cfg, model_for, max_batch=32, range_recovery=None
         for i, f in zip(idx, dec.decode_jobs([jobs[i] for i in idx], max_batch=max_batch, models=models)):
             frames[i] = f
     return jobs, frames, decoders
+
+
+def recovery_is_layer(range_recovery):
+    from .recovery import recovery_mode
+    return recovery_mode(range_recovery) == "layer"
+
+
+def frames_match(job, x):
+    """None for a format-3 job (nothing to compare); else whether the decoded frames ``x`` have the sender's CRC-32."""
+    if job.get("crc") is None:
+        return None
+    return container.frames_crc(x) == job["crc"]
 
 
 def build_parser():
@@ -122,6 +146,7 @@ def main(argv=None):
     data = np.load(args.data_npy, mmap_mode="r") if os.path.exists(args.data_npy) else None
     os.makedirs(args.output_path, exist_ok=True)
     note = cli.recovery_note(decoders[0])
+    mismatches = 0
     for (path, _), job, x in zip(streams, jobs, frames):
         name = "v%d_q%d_thr%.2f" % (job["vid"], job["q"], job["thr"])
         cli.check_numerics(x, f"{os.path.basename(path)}", note)
@@ -132,8 +157,14 @@ def main(argv=None):
         if data is not None:
             gt = np.asarray(data[job["vid"]], dtype=np.float32) / 255.0
             line += " PSNR %.3f" % np.mean([cli.cal_psnr(x[t], gt[t]) for t in range(len(x))])
+        same = frames_match(job, x)
+        if same is not None:             # format 4: the receiver's frames against the sender's checksum
+            line += ", frames: match" if same else ", frames: MISMATCH"
+            mismatches += 0 if same else 1
         log(line)
     log(f"decoded {len(jobs)} job stream(s) into {args.output_path}")
+    if mismatches:
+        sys.exit(f"{mismatches} job(s) decoded to other frames than the sender's (frames: MISMATCH)")
 
 
 if __name__ == "__main__":

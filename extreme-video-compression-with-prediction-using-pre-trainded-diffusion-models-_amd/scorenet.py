@@ -112,16 +112,17 @@ def range_sites(program, cond_emb=False):
 
 
 class _Act:
-    """An NHWC activation with lazily computed, cached per-channel moments."""
-    __slots__ = ("t", "_stats")
+    """An NHWC activation with lazily computed, cached per-channel moments (``invariant``: pixel ranges from H*W only)."""
+    __slots__ = ("t", "_stats", "invariant")
 
-    def __init__(self, t, stats=None):
+    def __init__(self, t, stats=None, invariant=False):
         self.t = t
         self._stats = stats
+        self.invariant = invariant
 
     def stats(self):
         if self._stats is None:
-            self._stats = L.chan_stats(self.t)
+            self._stats = L.chan_stats(self.t, invariant=self.invariant)
         return self._stats
 
 
@@ -204,7 +205,18 @@ class ScoreNet(DdpmWrapper):
     ARCH = "unetmore"  # scorenet_pseudo3d.Pseudo3dScoreNet: "unetmorepseudo3d"
     RANGE_SITES = True  # per-site range events and ``demote`` (range_sites); the pseudo-3-D networks use no fp16 split
 
-    def __init__(self, config, state_dict, device="cuda", prefix="", preactivate=False, use_graphs=False, demote=()):
+    def __init__(self, config, state_dict, device="cuda", prefix="", preactivate=False, use_graphs=False, demote=(),
+                 batch_invariant=False):
+        # batch_invariant=True: every launch of a forward asks the library for its batch-invariant plan:
+        # the numbers of one sample then depend on that sample's inputs, its label and the weights only -- not on the batch
+        # size, the sample's row or the other rows.  Its own fixed arithmetic: NOT the bits of the default mode at any B.
+        # ``invariant_view()`` gives such a network on the packed weights of an existing one.
+        self.batch_invariant = bool(batch_invariant)
+        if self.batch_invariant and (self.SPADE or self.ARCH != "unetmore"):
+            raise NotImplementedError("batch_invariant is built for the concat-conditioned score network (ScoreNet) only")
+        if self.batch_invariant and demote:
+            raise ValueError("batch-invariant mode does not combine with demoted sites (range recovery): a receiver could not "
+                             "know which layers the sender demoted")
         L.hip_lib()   # fail loudly before touching anything else
         # preactivate=False: AdaGN + SiLU is fused into the 3x3 convolutions' operand load (evaluated once per
         # filter tap, costs MFMA issue slots); True: applied once per tensor by evc_affine_act_nhwc_f32 and the
@@ -226,6 +238,8 @@ class ScoreNet(DdpmWrapper):
         # :282-285); noise_in_cond, the schedule (linear / cosine) and the Gamma buffers: DdpmWrapper
         self.cond_emb = bool(getattr(m, "cond_emb", False))
         self._init_wrapper(m, self.d.sigma_begin, self.d.sigma_end, self.d.num_classes)
+        if self.batch_invariant and self.noise_in_cond:
+            raise NotImplementedError("batch_invariant with noise_in_cond: the conditioning noise is drawn per batch")
         if (self.cond_emb or self.noise_in_cond) and self.SPADE:
             raise NotImplementedError("cond_emb / noise_in_cond are built for the concat-conditioned network only")
         self.embed_dim = self._embed_dim()
@@ -267,8 +281,55 @@ class ScoreNet(DdpmWrapper):
         self._bounds_by_stream = {}      # concurrent clip groups run forwards on their own streams: one arena each
         self._bounds = None
         self._bound_next = 0
+        self._bound_batch = 1            # words per slot: the batch in batch-invariant mode (one word per sample)
         if demote:
             self.demote(demote)
+
+    # ---- every launch that plans by batch goes through these: the mode is passed on each call, explicitly ----------
+    def _conv(self, *a, **kw):
+        return L.conv2d_nhwc(*a, invariant=self.batch_invariant, **kw)
+
+    def _act(self, t, stats=None):
+        return _Act(t, stats, invariant=self.batch_invariant)
+
+    def _gn(self, *a, **kw):
+        return L.gn_coeffs(*a, invariant=self.batch_invariant, **kw)
+
+    def _mbound(self, *a, **kw):
+        return L.moments_bound(*a, invariant=self.batch_invariant, **kw)
+
+    def _attention(self, *a, **kw):
+        return L.attention(*a, invariant=self.batch_invariant, **kw)
+
+    def _fuse_ok(self, *a, **kw):
+        return L.conv_fused_1x1_supported(*a, invariant=self.batch_invariant, **kw)
+
+    # ---- batch-invariant view --------------------------------------------------------------------
+    def invariant_view(self):
+        """A batch-invariant network on THIS network's packed weights (no second copy of them): its own AdaGN table, bound
+        arenas, side streams and captured graphs; weights, program and range-event sites are shared.  Demoting a site of
+        either network afterwards is refused by the view (its arithmetic is fixed)."""
+        import copy
+        if self.batch_invariant:
+            return self
+        if self.SPADE or self.ARCH != "unetmore" or self.noise_in_cond:
+            raise NotImplementedError("batch_invariant is built for the concat-conditioned score network (ScoreNet) only")
+        if self._demoted:
+            raise ValueError("batch-invariant mode does not combine with demoted sites (range recovery)")
+        # SHARED on purpose (one object, both networks): ``w`` (the packed weights: no second 1 GB copy), ``program``,
+        # ``sites`` / ``site_words`` / ``_site_of`` (range events are reported, never acted on, by the view), the schedule
+        # buffers, and ``_demoted`` / ``_attn_f32`` / ``_unfused``: they are only ever mutated in place by ``demote`` of
+        # the base network, and a non-empty ``_demoted`` makes the view refuse its next forward (its arithmetic is
+        # fixed; a repacked weight would change its bits).  OWN state: everything a forward writes, reset below.
+        v = copy.copy(self)
+        v.batch_invariant = True
+        v.taps = None
+        v._rows, v._row_tensors = {}, {}
+        v._table = torch.zeros_like(self._table)
+        v._n_rows = 0
+        v._graphs, v._side_streams, v._bounds_by_stream = {}, {}, {}
+        v._bounds, v._bound_next = None, 0
+        return v
 
     # ---- range-event sites ---------------------------------------------------------------------
     def _set_site_args(self):
@@ -295,6 +356,8 @@ class ScoreNet(DdpmWrapper):
         fp16-split kernel only), and the captured HIP graphs (pointers to the old packs) are dropped.  A demoted site
         still runs its range test but reports to its own site word only.  Sticky.  Returns the newly demoted sites."""
         import time
+        if self.batch_invariant:
+            raise ValueError("batch-invariant mode does not combine with demoted sites (range recovery)")
         new = [k for k in dict.fromkeys(self._site_ids(sites)) if k not in self._demoted]
         if not new:
             return []
@@ -433,14 +496,22 @@ class ScoreNet(DdpmWrapper):
         if not new:
             return
         R = len(new)
-        e = self._embedding([k[0] if self.cond_emb else k for k in new]).to(self.device).reshape(1, 1, R, self.embed_dim).contiguous()
+        if self.batch_invariant:
+            # the rows as a batch of R one-pixel images under the invariant plan: a label's row does not depend on which
+            # other labels happen to be new in the same call
+            return self._prepare_rows(new, (R, 1, 1))
+        return self._prepare_rows(new, (1, 1, R))
+
+    def _prepare_rows(self, new, shape):
+        R = len(new)
+        e = self._embedding([k[0] if self.cond_emb else k for k in new]).to(self.device).reshape(*shape, self.embed_dim).contiguous()
         w0, w1 = self.w[0], self.w[1]
-        t = L.conv2d_nhwc(e, w0["w"], w0["co"], 1, 1, bias=w0["b"])                       # Linear(ngf -> 4ngf)
-        t = L.conv2d_nhwc(t, w1["w"], w1["co"], 1, 1, bias=w1["b"], act_in=L.ACT_SILU)    # act -> Linear
+        t = self._conv(e, w0["w"], w0["co"], 1, 1, bias=w0["b"])                       # Linear(ngf -> 4ngf)
+        t = self._conv(t, w1["w"], w1["co"], 1, 1, bias=w1["b"], act_in=L.ACT_SILU)    # act -> Linear
         if self.cond_emb:                # temb = cat([temb, Embedding(cond_mask)]) (ncsnpp_more.py:282-285); rows are label-major
             emb = self.cond_table[torch.tensor([k[1] for k in new], device=self.device)]
-            t = torch.cat([t.reshape(R, -1), emb], 1).reshape(1, 1, R, -1).contiguous()
-        rows = L.conv2d_nhwc(t, self.dense_w, self.ss_total, 1, 1, bias=self.dense_b, act_in=L.ACT_SILU)
+            t = torch.cat([t.reshape(R, -1), emb], 1).reshape(*shape, -1).contiguous()
+        rows = self._conv(t, self.dense_w, self.ss_total, 1, 1, bias=self.dense_b, act_in=L.ACT_SILU)
         base = self._n_rows
         if base + R > self._table.shape[0]:
             grown = torch.zeros((max(2 * self._table.shape[0], base + R), self.ss_total), device=self.device)
@@ -464,7 +535,7 @@ class ScoreNet(DdpmWrapper):
     def _adagn(self, parts, hw, ch, seg, rows, bound=None, site=None):
         off, c = seg
         assert c == ch
-        return L.gn_coeffs(parts, hw, num_groups(ch), 1e-5, mode=2, ss=self._table[:, off:off + 2 * c], row=rows,
+        return self._gn(parts, hw, num_groups(ch), 1e-5, mode=2, ss=self._table[:, off:off + 2 * c], row=rows,
                            bound=bound, site=site)
 
     def _side_stream(self, main):
@@ -476,9 +547,11 @@ class ScoreNet(DdpmWrapper):
         return st
 
     def _bound_slot(self, n=1):
-        """n zeroed device words of this forward's arena (element bounds for the fp16-split kernels on raw inputs)."""
+        """n zeroed device words of this forward's arena (element bounds for the fp16-split kernels on raw inputs); in
+        batch-invariant mode n words PER SAMPLE, sample-major (B, n) flattened."""
         if not self._f16_raw:
             return None
+        n *= self._bound_batch
         w = self._bounds[self._bound_next:self._bound_next + n]
         self._bound_next += n
         return w
@@ -502,13 +575,13 @@ class ScoreNet(DdpmWrapper):
             if fir is not None:
                 src, src1 = L.upfirdn2d_nhwc(x.t, *fir), None
             if "w2" in e:
-                return L.conv2d_nhwc(src, e["w2"], m["cout"], 1, 1, bias=e["b2"], src1=src1, in_bound=_f16_only(e["w2"], xbound),
+                return self._conv(src, e["w2"], m["cout"], 1, 1, bias=e["b2"], src1=src1, in_bound=_f16_only(e["w2"], xbound),
                                      out=out)
             return src
 
         Ho, Wo = (2 * H, 2 * W) if m["up"] else ((H // 2, W // 2) if m["down"] else (H, W))
         fuse = self.fuse_skip and "w2" in e and not self.preactivate and i not in self._unfused and \
-            L.conv_fused_1x1_supported(B, Ho, Wo, m["cout"], m["cout"], L.packed_arith(e["w1"]))
+            self._fuse_ok(B, Ho, Wo, m["cout"], m["cout"], L.packed_arith(e["w1"]))
         # The x-branch only depends on the block input: with `overlap_skip` it runs on a side stream while the main stream
         # does the h-branch (FIR, Conv_0, its moments), so its small latency-bound launches (the 1x1 convolution, its
         # split-K combine) hide behind Conv_0 instead of sitting in front of Conv_1.  Joined by an event before Conv_1.
@@ -528,7 +601,7 @@ class ScoreNet(DdpmWrapper):
                 done.record(side)
         if fir is not None:
             hf = L.upfirdn2d_nhwc(x.t, *fir, coef=coef0, act=L.ACT_SILU)
-            h1 = _Act(*L.conv2d_nhwc(hf, e["w0"], m["cout"], 3, 3, bias=e["b0"], want_stats=True))
+            h1 = self._act(*self._conv(hf, e["w0"], m["cout"], 3, 3, bias=e["b0"], want_stats=True))
         elif self.preactivate:
             cin = m["cin"]
             act = torch.empty((B, H, W, cin), device=self.device, dtype=torch.float32)
@@ -536,9 +609,9 @@ class ScoreNet(DdpmWrapper):
             L.affine_act(x.t, coef0, L.ACT_SILU, out=L.Cols(act, 0, c0))
             if skip is not None:
                 L.affine_act(skip.t, coef0, L.ACT_SILU, out=L.Cols(act, c0, cin - c0), coef_col=c0)
-            h1 = _Act(*L.conv2d_nhwc(act, e["w0"], m["cout"], 3, 3, bias=e["b0"], want_stats=True))
+            h1 = self._act(*self._conv(act, e["w0"], m["cout"], 3, 3, bias=e["b0"], want_stats=True))
         else:
-            h1 = _Act(*L.conv2d_nhwc(x.t, e["w0"], m["cout"], 3, 3, bias=e["b0"], src1=s1, coef=coef0, act_in=L.ACT_SILU,
+            h1 = self._act(*self._conv(x.t, e["w0"], m["cout"], 3, 3, bias=e["b0"], src1=s1, coef=coef0, act_in=L.ACT_SILU,
                                      want_stats=True))
         H1, W1 = h1.t.shape[1], h1.t.shape[2]
         coef1 = self._adagn([h1.stats()], H1 * W1, m["cout"], e["ss1"], rows, site=self._site("res1", i))
@@ -553,13 +626,13 @@ class ScoreNet(DdpmWrapper):
             # Conv_1 + Conv_2 in one launch (models/better/layerspp.py:603-624): x2 = the block input (both halves of a skip
             # concat read in place) or its FIR-resampled copy; |FIR(x)| <= max |x| (taps sum to 1), so x's bound serves both
             x2 = (xs, None, e["w2"], xbound) if xs is not None else (x.t, s1, e["w2"], xbound)
-            return _Act(*L.conv2d_nhwc(h1.t, e["w1"], m["cout"], 3, 3, bias=e["b12"], coef=coef1, act_in=L.ACT_SILU,
+            return self._act(*self._conv(h1.t, e["w1"], m["cout"], 3, 3, bias=e["b12"], coef=coef1, act_in=L.ACT_SILU,
                                        out_scale=INV_SQRT2, want_stats=True, x2=x2))
         if self.preactivate:
             h1a = L.affine_act(h1.t, coef1, L.ACT_SILU)
-            return _Act(*L.conv2d_nhwc(h1a, e["w1"], m["cout"], 3, 3, bias=e["b1"], res=xs, out_scale=INV_SQRT2,
+            return self._act(*self._conv(h1a, e["w1"], m["cout"], 3, 3, bias=e["b1"], res=xs, out_scale=INV_SQRT2,
                                        want_stats=True))
-        return _Act(*L.conv2d_nhwc(h1.t, e["w1"], m["cout"], 3, 3, bias=e["b1"], coef=coef1, act_in=L.ACT_SILU,
+        return self._act(*self._conv(h1.t, e["w1"], m["cout"], 3, 3, bias=e["b1"], coef=coef1, act_in=L.ACT_SILU,
                                    res=xs, out_scale=INV_SQRT2, want_stats=True))
 
     def _attn(self, i, m, x):
@@ -568,39 +641,47 @@ class ScoreNet(DdpmWrapper):
         B, H, W, C = x.t.shape
         hd = self.d.n_head_channels
         heads = 1 if C < hd else C // hd
-        coef = L.gn_coeffs([x.stats()], H * W, num_groups(C), 1e-6, mode=1, gamma=e["gamma"], beta=e["beta"],
+        coef = self._gn([x.stats()], H * W, num_groups(C), 1e-6, mode=1, gamma=e["gamma"], beta=e["beta"],
                            site=self._site("attn_norm", i))
         qkvb = self._bound_slot(3)
         if qkvb is None:
             obound = None
-            qkv = L.conv2d_nhwc(x.t, e["wqkv"], 3 * C, 1, 1, bias=e["bqkv"], coef=coef)
+            qkv = self._conv(x.t, e["wqkv"], 3 * C, 1, 1, bias=e["bqkv"], coef=coef)
         else:
             # element bounds of q, k, v from the projection's fused moments (one small launch); the attention output is
             # a convex combination of value rows, so max |o| <= max |v|: v's bound also serves the output projection
-            qkv, qst = L.conv2d_nhwc(x.t, e["wqkv"], 3 * C, 1, 1, bias=e["bqkv"], coef=coef, want_stats=True)
-            L.moments_bound(qst, 0, C, qkvb, site=self._site("attn_qkv", i))
-            obound = _f16_only(e["wo"], qkvb[2:3])
-        o = L.attention(qkv.view(B, H * W, 3 * C), C, heads, bounds=None if i in self._attn_f32 else qkvb)
-        return _Act(*L.conv2d_nhwc(o.view(B, H, W, C), e["wo"], C, 1, 1, bias=e["bo"], res=x.t,
+            qkv, qst = self._conv(x.t, e["wqkv"], 3 * C, 1, 1, bias=e["bqkv"], coef=coef, want_stats=True)
+            self._mbound(qst, 0, C, qkvb, site=self._site("attn_qkv", i))
+            # v's bound: one word, or in batch-invariant mode every sample's third word gathered into B consecutive ones
+            obound = _f16_only(e["wo"], qkvb.view(B, 3)[:, 2].contiguous() if self.batch_invariant else qkvb[2:3])
+        o = self._attention(qkv.view(B, H * W, 3 * C), C, heads, bounds=None if i in self._attn_f32 else qkvb)
+        return self._act(*self._conv(o.view(B, H, W, C), e["wo"], C, 1, 1, bias=e["bo"], res=x.t,
                                    out_scale=INV_SQRT2, want_stats=True, in_bound=obound))
 
     @torch.no_grad()
     def forward_rows(self, x, rows, cond=None):
         """x: (B, C*num_frames, H, W) NCHW, rows: int32 (B,) device tensor of AdaGN-table rows."""
+        if self.batch_invariant and self._demoted:
+            raise ValueError("batch-invariant mode does not combine with demoted sites (range recovery)")
+        return self._forward_rows(x, rows, cond)
+
+    def _forward_rows(self, x, rows, cond=None):
         d = self.d
         prog = self.program
         B, _, H, W = x.shape
+        self._bound_batch = B if self.batch_invariant else 1
+        nb = 256 * self._bound_batch
         if self._f16_raw:
             # one arena per stream (concurrent clip groups run their forwards on their own streams).  Inside a HIP-graph
             # capture every graph owns its arena: all captures share one capture stream, and graphs replayed
             # concurrently on different streams would race on a shared one.
             if torch.cuda.is_current_stream_capturing():
-                self._bounds = torch.empty(256, device=self.device, dtype=torch.int32)
+                self._bounds = torch.empty(nb, device=self.device, dtype=torch.int32)
             else:
                 key = torch.cuda.current_stream().cuda_stream
                 self._bounds = self._bounds_by_stream.get(key)
-                if self._bounds is None:
-                    self._bounds = self._bounds_by_stream[key] = torch.empty(256, device=self.device, dtype=torch.int32)
+                if self._bounds is None or self._bounds.numel() != nb:
+                    self._bounds = self._bounds_by_stream[key] = torch.empty(nb, device=self.device, dtype=torch.int32)
             self._bounds.zero_()          # one memset per forward; slots are handed out in program order
             self._bound_next = 0
         # test hook (tests/test_gpu_scorenet.py): ``self.taps = {}`` before a call collects every module's output, NCHW,
@@ -614,7 +695,7 @@ class ScoreNet(DdpmWrapper):
         i = 2
         m = prog[i]
         xin = self._pack_input(x, cond, self.w[i]["cin_pad"])
-        hs = [tap(i, _Act(*L.conv2d_nhwc(xin, self.w[i]["w"], m["cout"], 3, 3, bias=self.w[i]["b"], want_stats=True)))]
+        hs = [tap(i, self._act(*self._conv(xin, self.w[i]["w"], m["cout"], 3, 3, bias=self.w[i]["b"], want_stats=True)))]
         i += 1
         n_lvl = len(d.ch_mult)
         for lvl in range(n_lvl):
@@ -652,11 +733,11 @@ class ScoreNet(DdpmWrapper):
         """Final GroupNorm + SiLU fused into the output convolution's load (ncsnpp_more.py:380-388)."""
         e = self.w[i]
         B, H, W, C = h.t.shape
-        coef = L.gn_coeffs([h.stats()], H * W, num_groups(C), 1e-5, mode=1, gamma=e["gamma"], beta=e["beta"],
+        coef = self._gn([h.stats()], H * W, num_groups(C), 1e-5, mode=1, gamma=e["gamma"], beta=e["beta"],
                            site=self._site("norm", i))
         co = self.program[i + 1]["cout"]
         out = torch.empty((B, H, W, _pad16(co)), device=h.t.device, dtype=torch.float32)
-        L.conv2d_nhwc(h.t, self.w[i + 1]["w"], co, 3, 3, bias=self.w[i + 1]["b"], coef=coef, act_in=L.ACT_SILU, out=out)
+        self._conv(h.t, self.w[i + 1]["w"], co, 3, 3, bias=self.w[i + 1]["b"], coef=coef, act_in=L.ACT_SILU, out=out)
         return out, co
 
     def _forward(self, x, rows, cond):
@@ -727,7 +808,7 @@ def build_score_network(config, state_dict, device="cuda", **kw):
     arch = getattr(config.model, "arch", "unetmore")
     if arch == "unet":
         from .unet_ddpm import UNetDDPM
-        return UNetDDPM(config, state_dict, device=device)
+        return UNetDDPM(config, state_dict, device=device, batch_invariant=kw.get("batch_invariant", False))
     if arch in ("unetmorepseudo3d", "unetmore3d"):
         from .scorenet_pseudo3d import Conv3dScoreNet, Pseudo3dScoreNet
         return (Conv3dScoreNet if arch == "unetmore3d" else Pseudo3dScoreNet)(config, state_dict, device=device, **kw)

@@ -89,7 +89,9 @@ class Pseudo3dScoreNet(ScoreNet):
     ARCH = "unetmorepseudo3d"
     RANGE_SITES = False
 
-    def __init__(self, config, state_dict, device="cuda", prefix="", use_graphs=False, **_):
+    def __init__(self, config, state_dict, device="cuda", prefix="", use_graphs=False, batch_invariant=False, **_):
+        if batch_invariant:
+            raise NotImplementedError("batch_invariant is built for the concat-conditioned score network (ScoreNet) only")
         super().__init__(config, state_dict, device=device, prefix=prefix, preactivate=False, use_graphs=use_graphs)
         if self.cond_emb or self.noise_in_cond:
             raise NotImplementedError("cond_emb / noise_in_cond are built for the 2-D concat-conditioned network only")

@@ -70,7 +70,9 @@ def build_program(ngf, mode, n_in):
 class UNetDDPM(DdpmWrapper):
     """HIP implementation of ``UNet_DDPM`` (eval mode, dropout 0; output_all_frames off)."""
 
-    def __init__(self, config, state_dict, device="cuda", prefix=""):
+    def __init__(self, config, state_dict, device="cuda", prefix="", batch_invariant=False):
+        if batch_invariant:
+            raise NotImplementedError("batch_invariant is built for the concat-conditioned score network (ScoreNet) only")
         m_ = config.model
         mode_ = getattr(config, "mode", "deep")
         widths = sorted({m["ch"] for _, _, m in build_program(m_.ngf, mode_, 1) if m["kind"] == "attn"})

@@ -213,6 +213,9 @@ typedef struct {
      * bound (as in_bound, required).  `bias` must already hold the sum of both convolutions' biases. */
     const float* x2_src0; const float* x2_src1; int x2_C0; int x2_C1; int x2_ld0; int x2_ld1;
     const float* x2_w_packed; const unsigned* x2_bound;
+    int invariant;         /* 0 = the default plan.  1 = BATCH-INVARIANT mode (see below): the plan is a function of the layer
+                              (H, W, C0 + C1, fused-operand channels, Co, KH, KW, arith, on-load mode) only, B sizes the grid;
+                              in_bound / x2_bound then point to B words, one per sample. */
 } evc_conv_args;
 int evc_conv_co_pad(int Co);
 long long evc_conv_packed_floats(int Co, int Ci, int KH, int KW);
@@ -243,6 +246,48 @@ int evc_conv_fused_1x1_supported(const evc_conv_args* a);   /* 1: these argument
 int evc_conv_stats_splits(const evc_conv_args* a);
 long long evc_conv_workspace_bytes(const evc_conv_args* a);
 int evc_conv2d_nhwc_f32(const evc_conv_args* a, float* ws, void* stream);
+
+/* ---- batch-invariant mode --------------------------------------------------------------------
+ * Opt-in per call (evc_conv_args::invariant, the *_sample_* / *_invariant_* entry points below; never process-wide: one
+ * process may run default and invariant networks side by side).  In this mode the numbers computed for one sample are a
+ * function of that sample's inputs and the weights only -- not of B, of the sample's row or of the other rows:
+ *   - convolutions: kernel family, tile, split-K count and boundaries and the unequal cut are those of the default plan of the
+ *     same layer at B = 9, without the K-split tail and ignoring evc_conv_set_option; tiles that are not whole fractions of a
+ *     sample (H*W % tile != 0) always take the per-element epilogue; the fused moments have one producer and one run length
+ *     per layer (evc_conv_stats_splits: 0 = run evc_chan_stats_f32, at every B alike);
+ *   - element bounds of the fp16 split: one word PER SAMPLE (bound_bits[b], bound_bits[b * n_ranges + z]); a pixel is scaled
+ *     from its own sample's word.  conv_split_rr_kernel / conv_wide_kernel keep one scale per tile, so a bounded or fused
+ *     operand needs H*W % tile == 0 there (EVC_EUNSUPPORTED otherwise; evc_conv_fused_1x1_supported says 0); the 1x1
+ *     kernel scales per pixel row;
+ *   - attention: waves per workgroup and key parts from (heads, N, D) only (the default plan at B = 9, always the
+ *     with-workspace one), evc_attention_set_option ignored.
+ * The bits of this mode are NOT those of the default mode at any particular B.  evc_invariant_plan_revision() is bumped
+ * whenever a change alters them (job streams carry it). */
+#define EVC_INVARIANT_REF_BATCH 9      /* the batch whose default plan is the invariant plan (convolutions and attention) */
+int evc_invariant_plan_revision(void);
+/* The whole plan of a convolution, without a launch: the kernel instance (as evc_conv_kernel_name), the pixel x channel
+ * tile, the K split (count, K-steps per split, first chunk of the second piece of an unequal 2-way cut or 0), the K-split
+ * tail (pixel tiles, ways; 0 / 1 = none), the fused-moment runs per image (evc_conv_stats_splits) and whether a fused 1x1
+ * operand is accepted. */
+typedef struct {
+    char kernel[96];
+    int tile_m, tile_n, splits, steps_per_split, cut_chunk, tail_tiles, tail_splits, stats_runs, fused_1x1;
+} evc_conv_plan;
+int evc_conv_plan_query(const evc_conv_args* a, evc_conv_plan* out);
+/* evc_gn_coeffs_bound_site_f32 / evc_moments_bound_site_f32 with one bound word per sample: sample b raises
+ * bound_bits[b] (gn_coeffs) or bound_bits[b * n_ranges + z] (moments).  site_events may be NULL. */
+int evc_gn_coeffs_bound_sample_f32(const float* part0, int nsplit0, int C0, const float* part1, int nsplit1, int C1, int B,
+                                   int HW, int groups, float eps, int mode, const float* gamma, const float* beta,
+                                   const float* ss, int ss_ld, const int* row, float* coef_a, float* coef_s,
+                                   unsigned* bound_bits, unsigned* events, unsigned* site_events, int site, void* stream);
+int evc_moments_bound_sample_f32(const float* part, int nsplit, int C, int c_begin, int c_count, int n_ranges, int B,
+                                 unsigned* bound_bits, unsigned* events, unsigned* site_events, int site, void* stream);
+/* Attention with the batch-invariant plan.  bounds: NULL = the f32-MFMA kernel, else [B][3] words (q, k, v of each sample)
+ * = the fp16-split kernel.  ws: evc_attention_invariant_workspace_bytes() bytes (NULL when that is 0). */
+long long evc_attention_invariant_workspace_bytes(int B, int heads, int N, int D);
+int evc_attention_invariant_f32(const float* q, const float* k, const float* v, int ld_qkv, float* out, int ld_out, int B,
+                                int heads, int N, int D, float scale, const unsigned* bounds, float* ws, void* stream);
+
 /* Measurement hook: the same launch with two hipEvent_t handles (either may be NULL) recorded on `stream` immediately before
  * the convolution kernel and immediately after it, i.e. before the split-K combine kernel: the interval is the convolution
  * kernel's own duration, the figure rocprofv3 --kernel-trace reports for it (bench.py's roofline leg). */

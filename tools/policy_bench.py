@@ -39,6 +39,8 @@ def main():
     ap.add_argument("--qs", type=int, nargs="+", default=[4, 5])             # city_sender.py:504 q range of the sweep
     ap.add_argument("--n-thresholds", type=int, default=28)                  # city_sender.py:505-508
     ap.add_argument("--noise", choices=["torch", "evc"], default="torch")
+    ap.add_argument("--batch-invariant", action="store_true",
+                    help="run the sweep in the score network's batch-invariant mode (needs --noise evc)")
     a = ap.parse_args()
     L.hip_lib()
     cfg = default_config(192, 192, 128, subsample=a.subsample)
@@ -58,6 +60,7 @@ def main():
     stats = {}
     t0 = time.perf_counter()
     res = P.run_policy(dec, models, clips, a.qs, thresholds, P.PsnrMetric(), max_batch=a.max_batch, stats=stats, noise=a.noise,
+                       batch_invariant=a.batch_invariant,
                        log=lambda m: print(f"[policy_bench {time.strftime('%H:%M:%S')}] {m}", file=sys.stderr, flush=True))
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
@@ -82,7 +85,7 @@ def main():
     print(json.dumps({
         "workload": f"{a.videos} video(s) x q {a.qs} x {len(thresholds)} PSNR thresholds = {jobs} sender jobs of 30 frames "
                     f"(city_sender.py:495-607), DDPM-{a.subsample}, full-size network, synthetic clips / seeded weights",
-        "noise": a.noise, "seconds": round(el, 2), "noise_host_seconds": round(stats.get("noise_host_seconds", 0.0), 3),
+        "noise": a.noise, "batch_invariant": a.batch_invariant, "seconds": round(el, 2), "noise_host_seconds": round(stats.get("noise_host_seconds", 0.0), 3),
         "noise_kernel_b32_us": round(noise_us, 2), "noise_kernel_b32_tb_per_s": round(buf.numel() * 4 / noise_us / 1e6, 3),
         "jobs": jobs, "jobs_per_s": round(jobs / el, 3),
         "decoded_frames_per_s": round(jobs * 30 / el, 2),
