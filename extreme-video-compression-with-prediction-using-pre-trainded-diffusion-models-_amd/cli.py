@@ -92,6 +92,11 @@ def build_parser():
                         "bit at any --batch.  Job streams are then container format 4 (plan revision + CRC-32 of the frames). "
                         "Needs the replayable noise (--noise evc, selected when --noise is not given); refuses "
                         "--range-recovery layer")
+    p.add_argument("--share-generations", action="store_true",
+                   help="psnr / lpips policy: all thresholds of one (video, q) draw from one noise stream (stream id = index "
+                        "of the (video, q) pair) and each round generates once per distinct state -- the jobs that hold the "
+                        "same last two frames -- instead of once per job (DESIGN.md section 1).  The jobs of one (video, q) "
+                        "are then correlated samples; each is still what a receiver decodes from its own stream")
     p.add_argument("--range-recovery", choices=["off", "layer"], default=None,
                    help="layer: when a chunk raises an fp16-split range event, demote only the layers that raised it to the "
                         "bf16x6 split and regenerate the chunk with the same noise (default: EVC_RANGE_RECOVERY, else off: "
@@ -218,6 +223,8 @@ def main(argv=None):
         if args.noise is None:
             print("noise: evc (specification N1) because --batch-invariant frames are meant to be reproduced", flush=True)
             args.noise = "evc"
+    if args.share_generations and args.policy == "mask":
+        sys.exit("--share-generations applies to the psnr / lpips policy sweep (the mask policy has one job per clip)")
     if args.policy != "mask":
         if args.bitstream_dir and args.noise == "torch":
             sys.exit("--bitstream-dir with --noise torch: a job stream whose frames depend on torch's generators cannot be "
@@ -361,9 +368,14 @@ def main(argv=None):
         dec = ClipDecoder(net, None, cfg, S.get_sampler(args.sampler), range_recovery=args.range_recovery,
                           log=lambda m: print(f"[rank {rank}] {m}", flush=True))
         clips = {vid: torch.from_numpy(np.asarray(data[vid], dtype=np.float32) / 255.0) for vid in vids}
+        shared = dict(noise_streams="group", share=True, stats={}) if args.share_generations else {}
         res = P.run_policy(dec, models, clips, args.q, thresholds, metric, patch=args.patch, max_batch=args.policy_batch,
                            seed=args.seed, device=device, bpp_limit=args.bpp_limit, log=lambda m: print(f"[rank {rank}] {m}", flush=True),
-                           noise=args.noise, batch_invariant=args.batch_invariant)
+                           noise=args.noise, batch_invariant=args.batch_invariant, **shared)
+        if shared:
+            st = shared["stats"]
+            print(f"[rank {rank}] shared generations: {sum(st['states'])} sample-rounds generated for {sum(st['jobs_served'])} "
+                  f"job-rounds served ({len(st['states'])} rounds)", flush=True)
         if args.bitstream_dir:       # one replayable stream per reported job (receiver.py decodes them)
             from .receiver import write_job_streams
             written = write_job_streams(args.bitstream_dir, res, models, args.sampler, cfg)

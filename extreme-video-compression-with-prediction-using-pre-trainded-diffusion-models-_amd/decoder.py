@@ -214,7 +214,7 @@ class ClipDecoder:
         return torch.cat(out, dim=1)[:, :frames].contiguous()
 
     @torch.no_grad()
-    def decode_jobs(self, jobs, max_batch=32, models=None, size=None):
+    def decode_jobs(self, jobs, max_batch=32, models=None, size=None, share=False, stats=None):
         """Decode policy-job streams (``container.unpack_job`` dicts; possibly different q, masks and program lengths).
 
         All jobs advance in lockstep, as ``policy.run_policy`` advances them on the sender: each round every unfinished job
@@ -227,7 +227,19 @@ class ClipDecoder:
         crops its padded frames.  The generator settings of the streams (sampler, subsample steps, denoise) must be the ones
         this decoder was built with.  Format-4 jobs (``job["plan"]`` set: generated in batch-invariant mode) run their
         generation rounds on the network's batch-invariant view, in launches of their own: their frames are the sender's
-        bit for bit at any ``max_batch``.  Returns one (frames, 3, H, W) float32 device tensor per job."""
+        bit for bit at any ``max_batch``.
+
+        ``share=True`` does every distinct piece of work of a round once (the receiving side of ``run_policy(share=True)``;
+        nothing in a stream says it was shared, and nothing is guessed).  A key frame is identified by (q, its string bytes):
+        each distinct key frame of a round is decoded once, ``max_batch`` frames per call, whichever jobs name it.  A generation
+        state is (seed, stream id, format-4 flag, frames held, identities of the last two frames): the jobs of a state draw the
+        same noise for the same conditioning frames, so one sample is generated per state (``max_batch`` states per launch)
+        and each job keeps the first n frames its own segment names.  Streams of a sender with one noise stream per job have
+        distinct stream ids and merge on key frames only.  Jobs advance by segment, so two jobs share a state only while they
+        execute it in the same round.  Format-4 jobs keep launches of their own and their frames are the sender's bit for bit
+        either way.  ``stats``: optional dict; ``launch_sizes`` {samples in a launch: launches}, ``samples`` (generated samples),
+        ``job_rounds`` (generation segments executed) and ``key_frames_decoded`` are added up in it.
+        Returns one (frames, 3, H, W) float32 device tensor per job."""
         from . import container as Cn, sampler as S
         cfg = self.config
         mine = (getattr(cfg.sampling, "subsample", None) or 0, bool(cfg.sampling.denoise))
@@ -242,8 +254,18 @@ class ClipDecoder:
         model_of = (lambda q: self.elic) if models is None else (lambda q: models[q])
         ch = cfg.data.channels * cfg.data.num_frames
         x = [[] for _ in jobs]             # decoded frames per job
+        ids = [[] for _ in jobs]           # share: their identities, ("key", q, n) for the n-th distinct key string, ("gen", serial, t)
         pos = [0] * len(jobs)              # next segment
         used = [0] * len(jobs)             # key frames consumed
+        key_names, serial = {}, 0
+
+        def key_name(q, strings):          # (q, string bytes) -> a small id; the bytes are kept once
+            flat = (q,) + tuple(s for sl in strings[0] for p in sl for s in p) + tuple(strings[1])
+            return ("key", q, key_names.setdefault(flat, len(key_names)))
+
+        def count(name, n):
+            if stats is not None:
+                stats[name] = stats.get(name, 0) + n
         while True:
             todo = [i for i, job in enumerate(jobs) if pos[i] < len(job["segments"])]
             if not todo:
@@ -253,17 +275,60 @@ class ClipDecoder:
             # one seed per noise launch, one generation plan per score-network launch
             for seed, inv in sorted({(jobs[i]["seed"], jobs[i].get("plan") is not None) for i in gen}):
                 same = [i for i in gen if jobs[i]["seed"] == seed and (jobs[i].get("plan") is not None) == inv]
-                for c0 in range(0, len(same), max_batch):
-                    part = same[c0:c0 + max_batch]
-                    cond = torch.stack([torch.stack(x[i][-2:], 0) for i in part], 0).contiguous()
-                    keys = L.noise_keys([(jobs[i]["stream_id"], len(x[i])) for i in part], self.device)
+                states, at = [], {}                 # a state: the jobs that generate the same chunk; alone unless ``share``
+                for i in same:
+                    k = (jobs[i]["stream_id"], len(x[i]), ids[i][-1], ids[i][-2]) if share else i
+                    if k not in at:
+                        at[k] = len(states)
+                        states.append([])
+                    states[at[k]].append(i)
+                count("job_rounds", len(same))
+                count("samples", len(states))
+                for c0 in range(0, len(states), max_batch):
+                    part = states[c0:c0 + max_batch]
+                    heads = [members[0] for members in part]
+                    cond = torch.stack([torch.stack(x[i][-2:], 0) for i in heads], 0).contiguous()
+                    keys = L.noise_keys([(jobs[i]["stream_id"], len(x[i])) for i in heads], self.device)
                     pred = self.generate(cond, groups=1, invariant=inv, noise_fn=lambda tag, shape, keys=keys, seed=seed: L.noise_normal(
                         keys, shape, seed, 0 if tag == "init" else int(tag) + 1))
                     assert pred.shape[1] * pred.shape[2] == ch
-                    for k, i in enumerate(part):
-                        x[i] += [pred[k, t] for t in range(jobs[i]["segments"][pos[i]][1])]
+                    if stats is not None:
+                        h = stats.setdefault("launch_sizes", {})
+                        h[len(part)] = h.get(len(part), 0) + 1
+                    for k, members in enumerate(part):
+                        for i in members:
+                            n_i = jobs[i]["segments"][pos[i]][1]
+                            x[i] += [pred[k, t] for t in range(n_i)]
+                            ids[i] += [("gen", serial, t) for t in range(n_i)]
+                        serial += 1
             for q in sorted({jobs[i]["q"] for i in key}):
                 same = [i for i in key if jobs[i]["q"] == q]
+                if share:                  # every distinct key frame of the round once, then handed to the jobs that name it
+                    want, order = {}, []
+                    for i in same:
+                        for f in range(jobs[i]["segments"][pos[i]][1]):
+                            name = key_name(q, jobs[i]["key_strings"][used[i] + f])
+                            if name not in want:
+                                want[name] = jobs[i]["key_strings"][used[i] + f]
+                                order.append(name)
+                    shape = jobs[same[0]]["shape"]
+                    assert all(tuple(jobs[i]["shape"]) == tuple(shape) for i in same), "one frame size per decoder"
+                    frame_of = {}
+                    for c0 in range(0, len(order), max_batch):
+                        ks = [want[name] for name in order[c0:c0 + max_batch]]
+                        ys = [[[s for k_ in ks for s in k_[0][sl][p]] for p in range(2)] for sl in range(len(ks[0][0]))]
+                        zs = [s for k_ in ks for s in k_[1]]
+                        x_hat = model_of(q).decompress([ys, zs], shape)["x_hat"][:, :, :H, :W]
+                        for o, name in enumerate(order[c0:c0 + max_batch]):
+                            frame_of[name] = x_hat[o]
+                    count("key_frames_decoded", len(order))
+                    for i in same:
+                        n_i = jobs[i]["segments"][pos[i]][1]
+                        names = [key_name(q, jobs[i]["key_strings"][used[i] + f]) for f in range(n_i)]
+                        x[i] += [frame_of[name] for name in names]
+                        ids[i] += names
+                        used[i] += n_i
+                    same = []
                 while same:
                     part, n = [], 0
                     while same and (not part or n + jobs[same[0]]["segments"][pos[same[0]]][1] <= max_batch):
@@ -276,6 +341,7 @@ class ClipDecoder:
                     zs = [s for k_ in ks for s in k_[1]]
                     x_hat = model_of(q).decompress([ys, zs], shape)["x_hat"][:, :, :H, :W]
                     o = 0
+                    count("key_frames_decoded", len(ks))
                     for i in part:
                         n_i = jobs[i]["segments"][pos[i]][1]
                         x[i] += [x_hat[o + f] for f in range(n_i)]

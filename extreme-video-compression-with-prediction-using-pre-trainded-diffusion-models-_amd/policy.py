@@ -15,6 +15,10 @@ on which other jobs share its launch -- the batched sweep and a one-job-at-a-tim
 which a receiver can derive from the job stream alone; the result then carries the job's program (``segments``) and key-frame
 strings, everything ``container.pack_job`` needs.
 
+Shared rounds (``noise_streams="group", share=True``): all thresholds of one (video, q) then draw from ONE stream, so two jobs
+that hold the same frames would generate the same chunk; ``StateGrouper`` finds them by the identity of their last two frames
+and each round generates once per distinct state instead of once per job.
+
 Metrics: ``PsnrMetric`` is the reference's ``decide_5to5`` rule (accept while PSNR >= threshold, cal_psnr of
 city_sender.py:257-260).  ``CallableMetric`` is the hook for ``decide_5to5_lpips`` (accept while distance <=
 threshold): LPIPS needs torchvision's pretrained AlexNet, which cannot be fetched offline, so the metric is supplied
@@ -125,16 +129,60 @@ def coded_batch(model, x, patch):
 
 
 class _Job:
-    __slots__ = ("uid", "vid", "q", "thr", "x", "d", "bits", "round", "segments", "strings")
+    __slots__ = ("uid", "sid", "vid", "q", "thr", "x", "ids", "d", "bits", "round", "segments", "strings")
 
-    def __init__(self, uid, vid, q, thr):
+    def __init__(self, uid, vid, q, thr, sid=None):
         self.uid, self.vid, self.q, self.thr = uid, vid, q, thr
+        self.sid = uid if sid is None else sid          # id of the noise stream the job draws from
         self.x, self.d, self.bits, self.round = [], [], [], 0
+        self.ids = []                                   # identity of every frame of ``x`` (StateGrouper)
         self.segments, self.strings = [], []
 
 
+def key_id(vid, q, f):
+    """Identity of the decoded key frame f of (video, q): the sweep holds it once (``key_cache``)."""
+    return ("key", vid, q, f)
+
+
+def gen_id(serial, t):
+    """Identity of frame t of the chunk generated for the state with that serial number."""
+    return ("gen", serial, t)
+
+
+class StateGrouper:
+    """Which jobs of a round would generate the same chunk (host only; never looks at pixel data).
+
+    Under group noise streams a generation round is a function of (video, q, frames held, last two decoded frames): the
+    conditioning pair, the noise key (seed, group id, start frame = frames held, step) and the originals the candidates
+    are judged against.  Frames are compared by identity, ``key_id`` / ``gen_id``: two jobs hold the same generated frame
+    only when they were members of the same state in the round that made it, and the same key frame whenever they fell
+    back at the same frame index.  ``group`` numbers every state it returns with a serial of its own, which names the
+    frames generated for it."""
+
+    def __init__(self):
+        self.serial = 0
+
+    @staticmethod
+    def state_of(job):
+        return (job.vid, job.q, len(job.ids), job.ids[-1], job.ids[-2])
+
+    def group(self, jobs, share=True):
+        """jobs: the round's active jobs (``vid``, ``q``, ``ids``) -> [(serial, [member jobs])], states in the order of their
+        first member, members in the order given.  ``share=False``: every job is a state of its own."""
+        states, at = [], {}
+        for j in jobs:
+            k = self.state_of(j) if share else id(j)
+            if k not in at:
+                at[k] = len(states)
+                states.append((self.serial, []))
+                self.serial += 1
+            states[at[k]][1].append(j)
+        return states
+
+
 def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=30, max_batch=32, seed=0,
-               bpp_limit=1.0, device="cuda", log=None, noise_source=None, stats=None, noise="torch", batch_invariant=False):
+               bpp_limit=1.0, device="cuda", log=None, noise_source=None, stats=None, noise="torch", batch_invariant=False,
+               noise_streams="job", share=False):
     """The reference's sweep, batched.
 
     decoder:       ClipDecoder (only ``generate`` is used: the generator does not depend on q)
@@ -150,8 +198,26 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
     batch_invariant: generate on the score network's batch-invariant view: a job's frames then do not
                    depend on the launches it rode in, so a receiver reproduces them bit for bit at any batch size
                    (container format 4).  Needs noise="evc", as job streams do; every result then carries ``invariant=True``
-    stats:         optional dict, filled with the launch-size histogram {batch size: generation launches}, the number of
-                   generation rounds and of key frames coded, and the host seconds spent drawing noise
+    noise_streams: "job" -- every job draws from a stream of its own (stream id = the job's number) -- or "group": the stream id
+                   of a job is the index of its (video, q) pair in the sweep's order (video-major, then q), so all thresholds
+                   of one (video, q) share a stream.  The key of a round is then (seed, group id, start frame, step), for
+                   noise="torch" the generator seed mixes the same four; results carry ``stream_id`` = the group id, which is
+                   all a receiver needs.  Within one job no key is used twice, as before (the start frame strictly
+                   increases).  Two jobs of a group in different states at the same start frame draw the same noise for
+                   different conditioning frames: the jobs of one (video, q) are correlated samples, which is harmless
+                   because each job is reported on its own.  ``noise_source`` is keyed per (job, round) and does not combine
+                   with "group" (ValueError)
+    share:         generate once per distinct state instead of once per job (needs noise_streams="group").  Each round the
+                   active jobs are grouped by (video, q, frames held, identity of the last two frames) -- ``StateGrouper`` --,
+                   one conditioning pair per state is stacked (``max_batch`` states per launch), the metric is evaluated
+                   once per candidate frame of a state, and every member applies its own threshold and keeps the same frame
+                   tensors.  Jobs that diverge are in different states the next round; jobs that fall back to the same key
+                   frames merge again.  With ``batch_invariant`` every job's frames are bitwise what share=False gives under
+                   the same streams; in the default mode they differ in the last bits, as frames of launches of other
+                   shapes do
+    stats:         optional dict, filled with the launch-size histogram {samples (= states) in a launch: generation launches},
+                   the number of generation rounds and of key frames coded, the host seconds spent drawing noise, and per
+                   round the number of states generated (``states``) and of active jobs they served (``jobs_served``)
     Returns {(vid, q): [dict(thr, x (frames,3,H,W) float32 numpy, d (frames,) int, bits [..], bpp, segments, stream_id,
     seed, key_strings, shape)]} with, per (vid, q), the thresholds in the given order cut at the first one whose rate reaches
     ``bpp_limit`` bits per pixel (``if NN_bpp >= 1.0: break``, city_sender.py:563-564).  ``segments`` is the job's program in
@@ -163,6 +229,13 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
     if batch_invariant and noise != "evc":
         raise ValueError("batch_invariant needs noise='evc': torch's generators are not replayable by a receiver, so there is "
                          "nobody to reproduce the frames")
+    if noise_streams not in ("job", "group"):
+        raise ValueError(f"noise_streams must be 'job' or 'group', not {noise_streams!r}")
+    if noise_streams == "group" and noise_source is not None:
+        raise ValueError("noise_streams='group' does not combine with noise_source, which is keyed per (job, round)")
+    if share and noise_streams != "group":
+        raise ValueError("share=True needs noise_streams='group': jobs that draw from streams of their own never generate "
+                         "the same frames, so there is nothing to share")
     if batch_invariant:
         decoder._refuse_recovery()
     if noise == "evc" and noise_source is None:
@@ -171,12 +244,13 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
             raise NotImplementedError("noise='evc': noise specification N1 defines Gaussian noise only (config.model.gamma is set)")
         if float(getattr(cfg.sampling, "t_min", -1) or -1) > 0:
             raise NotImplementedError("noise='evc': noise specification N1 has no draw for a t_min > 0 start")
-    jobs, uid = [], 0
+    jobs, uid, gid = [], 0, 0
     for vid in clips:
         for q in qs:
             for thr in thresholds:
-                jobs.append(_Job(uid, vid, q, thr))
+                jobs.append(_Job(uid, vid, q, thr, sid=gid if noise_streams == "group" else None))
                 uid += 1
+            gid += 1
     gt_dev = {vid: c.to(device=device, dtype=torch.float32) for vid, c in clips.items()}
     H, W = next(iter(clips.values())).shape[-2:]
     key_cache = {}                  # (vid, q, frame) -> (x_hat on device, bits, strings)
@@ -198,6 +272,7 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
         for f in fs:
             xh, b, st = key_cache[(job.vid, job.q, f)]
             job.x.append(xh); job.bits.append(b); job.d.append(1); job.strings.append(st)
+            job.ids.append(key_id(job.vid, job.q, f))
         if len(fs):
             job.segments.append(("key", len(fs)))
 
@@ -207,10 +282,11 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
 
     def _noise_for(batch):
         if noise == "evc" and noise_source is None:      # the round's keys go up once; one launch per step for the whole batch
-            keys = L.noise_keys([(j.uid, len(j.x)) for j in batch], device)
+            keys = L.noise_keys([(j.sid, len(j.x)) for j in batch], device)
             return lambda tag, shape: L.noise_normal(keys, shape, seed, 0 if tag == "init" else int(tag) + 1)
 
-        def fn(tag, shape):      # one counter-based stream per (job, round, step): independent of the batch composition
+        def fn(tag, shape):      # one counter-based stream per (job, round, step) -- per (group, start frame, step) under group
+            # streams --: independent of the batch composition
             step = 0 if tag == "init" else int(tag) + 1
             out = torch.empty(shape, device=device, dtype=torch.float32)
             if noise_source is not None:
@@ -219,7 +295,8 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
                 return out
             for i, j in enumerate(batch):
                 g = torch.Generator(device=device)
-                g.manual_seed(((((int(seed) & 0xFFFFF) << 20 | j.uid) << 6 | j.round) << 10 | step) & (2 ** 63 - 1))
+                at = len(j.x) if noise_streams == "group" else j.round
+                g.manual_seed(((((int(seed) & 0xFFFFF) << 20 | j.sid) << 6 | at) << 10 | step) & (2 ** 63 - 1))
                 out[i] = torch.randn(shape[1:], device=device, dtype=torch.float32, generator=g)
             return out
         return fn
@@ -236,13 +313,16 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
             return out
         return timed
 
+    grouper = StateGrouper()
     while True:
         active = [j for j in jobs if len(j.x) < frames]
         if not active:
             break
+        states = grouper.group(active, share)            # [(serial, members)]: one generated sample per state
         fallback = []
-        for c0 in range(0, len(active), max_batch):
-            batch = active[c0:c0 + max_batch]
+        for c0 in range(0, len(states), max_batch):
+            part = states[c0:c0 + max_batch]
+            batch = [members[0] for _, members in part]                                       # a state's members hold the same frames
             cond = torch.stack([torch.stack(j.x[-2:], 0) for j in batch], 0).contiguous()     # (n, 2, 3, H, W)
             pred = decoder.generate(cond, noise_fn=noise_for(batch), groups=1,              # (n, 5, 3, H, W)
                                     invariant=True if batch_invariant else None)
@@ -254,18 +334,19 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
             flat_g = torch.cat([gt_dev[j.vid][len(j.x):len(j.x) + n_new[k]] for k, j in enumerate(batch)], 0)
             vals = metric.values(flat_p, flat_g)                 # every candidate frame of the launch in one call
             o = 0
-            for k, j in enumerate(batch):
-                acc = 0
-                for t in range(n_new[k]):
-                    if not metric.accept(vals[o + t], j.thr):
-                        break
-                    j.x.append(pred[k, t]); j.d.append(0); acc += 1
+            for k, (serial, members) in enumerate(part):
+                for j in members:                                # each member judges the state's candidates by its own threshold
+                    acc = 0
+                    for t in range(n_new[k]):
+                        if not metric.accept(vals[o + t], j.thr):
+                            break
+                        j.x.append(pred[k, t]); j.ids.append(gen_id(serial, t)); j.d.append(0); acc += 1
+                    j.round += 1
+                    if acc:
+                        j.segments.append(("gen", acc))
+                    if acc == 0:
+                        fallback.append(j)
                 o += n_new[k]
-                j.round += 1
-                if acc:
-                    j.segments.append(("gen", acc))
-                if acc == 0:
-                    fallback.append(j)
         if fallback:                 # city_sender.py:538-548: key-code the next two frames
             ensure_keys({(j.vid, j.q, f) for j in fallback for f in (len(j.x), len(j.x) + 1) if f < frames})
             for j in fallback:
@@ -273,8 +354,11 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
         if stats is not None:
             stats["rounds"] = stats.get("rounds", 0) + 1
             stats["key_frames_coded"] = len(key_cache)
+            stats.setdefault("states", []).append(len(states))
+            stats.setdefault("jobs_served", []).append(len(active))
         if log is not None:
-            log(f"policy round: {len(active)} active jobs, {len(fallback)} fell back to key frames")
+            log(f"policy round: {len(active)} active jobs" + (f" in {len(states)} states" if share else "") +
+                f", {len(fallback)} fell back to key frames")
 
     out = {}
     for j in jobs:
@@ -286,7 +370,7 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
             lst.append(None)
             continue
         lst.append(dict(thr=j.thr, x=torch.stack(j.x[:frames], 0).cpu().numpy(), d=np.asarray(j.d[:frames], dtype=np.int64),
-                        bits=list(j.bits), bpp=bpp, segments=list(j.segments), stream_id=j.uid, seed=int(seed),
+                        bits=list(j.bits), bpp=bpp, segments=list(j.segments), stream_id=j.sid, seed=int(seed),
                         key_strings=list(j.strings), shape=shapes[0], invariant=bool(batch_invariant)))
     return {k: [r for r in v if r is not None] for k, v in out.items()}
 

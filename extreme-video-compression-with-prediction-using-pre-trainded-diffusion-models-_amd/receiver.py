@@ -53,9 +53,11 @@ def read_job_streams(directory):
     return out
 
 
-def decode_streams(blobs, net, cfg, model_for, max_batch=32, range_recovery=None, log=print):
+def decode_streams(blobs, net, cfg, model_for, max_batch=32, range_recovery=None, log=print, share=False, stats=None):
     """blobs: [bytes]; model_for: q -> ElicModel (called once per q the streams name); -> ([job dict], [frames tensor]) in
-    the order given.  A stream coded under another entropy arithmetic raises ``container.CodecMismatch``."""
+    the order given.  A stream coded under another entropy arithmetic raises ``container.CodecMismatch``.  ``share`` and
+    ``stats`` are ``ClipDecoder.decode_jobs``': decode every distinct key frame and generate every distinct state of a round
+    once, and count the samples generated."""
     import copy
     from . import lib as L, sampler as S
     from .decoder import ClipDecoder
@@ -76,7 +78,8 @@ def decode_streams(blobs, net, cfg, model_for, max_batch=32, range_recovery=None
         dec = ClipDecoder(net, None, c, S.get_sampler(setting[0]), range_recovery=range_recovery, log=log)
         decoders.append(dec)
         idx = [i for i, j in enumerate(jobs) if (j["sampler"], j["subsample"], j["denoise"]) == setting]
-        for i, f in zip(idx, dec.decode_jobs([jobs[i] for i in idx], max_batch=max_batch, models=models)):
+        for i, f in zip(idx, dec.decode_jobs([jobs[i] for i in idx], max_batch=max_batch, models=models, share=share,
+                                                stats=stats)):
             frames[i] = f
     return jobs, frames, decoders
 
@@ -107,6 +110,10 @@ def build_parser():
     p.add_argument("--seed", type=int, default=1234, help="seed of the synthetic stand-ins (the sender's --seed)")
     p.add_argument("--range-recovery", choices=["off", "layer"], default=None, help="as city_sender.py")
     p.add_argument("--batch", type=int, default=32, help="jobs stacked per score-network launch")
+    p.add_argument("--share-generations", action="store_true",
+                   help="decode each distinct key frame and generate each distinct state of a round once, whichever jobs need "
+                        "it (streams of a city_sender.py --share-generations sweep share most of their rounds); --batch then "
+                        "counts states per launch")
     p.add_argument("--data_npy", type=str, default="city_bonn.npy", help="original clips: when present, per-job PSNR is printed")
     return p
 
@@ -141,8 +148,12 @@ def main(argv=None):
         sys.exit(f"missing ELIC checkpoint for q{q} (pass --synthetic)")
 
     log = lambda m: print(m, flush=True)  # noqa: E731
+    stats = {}
     jobs, frames, decoders = decode_streams([b for _, b in streams], net, cfg, model_for, max_batch=max(1, args.batch),
-                                            range_recovery=args.range_recovery, log=log)
+                                            range_recovery=args.range_recovery, log=log, share=args.share_generations, stats=stats)
+    if args.share_generations:
+        log(f"shared generations: {stats.get('samples', 0)} sample-rounds generated for {stats.get('job_rounds', 0)} job-rounds "
+            f"served, {stats.get('key_frames_decoded', 0)} key frames decoded")
     data = np.load(args.data_npy, mmap_mode="r") if os.path.exists(args.data_npy) else None
     os.makedirs(args.output_path, exist_ok=True)
     note = cli.recovery_note(decoders[0])

@@ -7,11 +7,14 @@ chunk).  Synthetic clips, seeded weights of the reference architecture, the PSNR
 are not available offline); thresholds are spread over the PSNR range the generated frames actually reach, so that the
 sweep contains both accepted chunks and key-frame fall-backs like a real one.
 
-    python tools/policy_bench.py [--videos 1] [--subsample 100] [--max-batch 32] [--noise torch|evc] > profiles/r03_policy_bench.json
+    python tools/policy_bench.py [--videos 1] [--subsample 100] [--max-batch 32] [--noise torch|evc] [--share] > profiles/r03_policy_bench.json
 
 ``--noise evc`` runs the sweep on the replayable noise of specification N1 (one HIP launch per sampler step for the whole batch)
 instead of one seeded torch.Generator per (job, round, step); the JSON line also reports the host seconds spent drawing noise and
-the noise kernel's write rate at B = 32.
+the noise kernel's write rate at B = 32.  ``--share`` runs the sweep with one noise stream per (video, q) and one generated sample
+per distinct state of a round (``run_policy(noise_streams="group", share=True)``); ``--noise-streams group`` alone keys the noise
+by group without sharing, the control the shared frames are compared with.  ``sample_forwards`` counts samples that went through
+the score network, so states under ``--share``.
 """
 import argparse
 import json
@@ -41,7 +44,14 @@ def main():
     ap.add_argument("--noise", choices=["torch", "evc"], default="torch")
     ap.add_argument("--batch-invariant", action="store_true",
                     help="run the sweep in the score network's batch-invariant mode (needs --noise evc)")
+    ap.add_argument("--share", action="store_true",
+                    help="generate once per distinct state of a round (selects --noise-streams group)")
+    ap.add_argument("--noise-streams", choices=["job", "group"], default=None,
+                    help="job (default): one noise stream per job; group: one per (video, q)")
     a = ap.parse_args()
+    if a.share and a.noise_streams == "job":
+        ap.error("--share needs --noise-streams group")
+    a.noise_streams = a.noise_streams or ("group" if a.share else "job")
     L.hip_lib()
     cfg = default_config(192, 192, 128, subsample=a.subsample)
     net = ScoreNet(cfg, synthetic.diffusion_state_dict(cfg, 1234))
@@ -60,7 +70,7 @@ def main():
     stats = {}
     t0 = time.perf_counter()
     res = P.run_policy(dec, models, clips, a.qs, thresholds, P.PsnrMetric(), max_batch=a.max_batch, stats=stats, noise=a.noise,
-                       batch_invariant=a.batch_invariant,
+                       batch_invariant=a.batch_invariant, noise_streams=a.noise_streams, share=a.share,
                        log=lambda m: print(f"[policy_bench {time.strftime('%H:%M:%S')}] {m}", file=sys.stderr, flush=True))
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
@@ -85,13 +95,15 @@ def main():
     print(json.dumps({
         "workload": f"{a.videos} video(s) x q {a.qs} x {len(thresholds)} PSNR thresholds = {jobs} sender jobs of 30 frames "
                     f"(city_sender.py:495-607), DDPM-{a.subsample}, full-size network, synthetic clips / seeded weights",
-        "noise": a.noise, "batch_invariant": a.batch_invariant, "seconds": round(el, 2), "noise_host_seconds": round(stats.get("noise_host_seconds", 0.0), 3),
+        "noise": a.noise, "batch_invariant": a.batch_invariant, "share": a.share, "noise_streams": a.noise_streams,
+        "seconds": round(el, 2), "noise_host_seconds": round(stats.get("noise_host_seconds", 0.0), 3),
         "noise_kernel_b32_us": round(noise_us, 2), "noise_kernel_b32_tb_per_s": round(buf.numel() * 4 / noise_us / 1e6, 3),
         "jobs": jobs, "jobs_per_s": round(jobs / el, 3),
         "decoded_frames_per_s": round(jobs * 30 / el, 2),
         "jobs_below_1bpp": kept, "generated_frames_kept": gen,
         "generation_rounds": stats.get("rounds"), "generation_launches": launches,
         "launch_size_histogram": {str(k): v for k, v in sorted(stats["launch_sizes"].items())},
+        "states_per_round": stats["states"], "jobs_served_per_round": stats["jobs_served"],
         "score_network_forwards": fwd, "sample_forwards": samples,
         "sample_forwards_per_s": round(samples / el, 1),
         "key_frames_coded": stats.get("key_frames_coded"),
