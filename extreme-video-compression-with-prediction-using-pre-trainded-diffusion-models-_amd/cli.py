@@ -15,6 +15,9 @@ reference's third per-job number, the FVD of the decoded clip against the origin
 HIP I3D network (fvd.py) and saved as ``fvd_<idx>.npy``.  Under a decision rule ``--bitstream-dir DIR`` writes one replayable
 job stream per reported job (container format 3; format 4 with ``--batch-invariant``) for ``city_receiver.py`` and runs the sweep on noise specification N1
 (``--noise evc``).  ``--gpus N`` (or ``torch.distributed.run``) block-shards the video range over N ranks, one GPU each.
+``--data_yuv FILE`` reads the clips from a Y4M or raw planar YUV 4:2:0 file instead of ``--data_npy`` (video_io.py: the
+reference's benchmark conventions, converted by the HIP kernels of csrc/yuv.hip), ``--yuv-out`` writes each job's decoded clip
+as ``.y4m`` and ``--yuv-metrics`` adds the PSNR of the reference's codec benchmark.
 """
 import argparse
 import os
@@ -105,7 +108,54 @@ def build_parser():
                    help="i3d_pretrained_400.pt (InceptionI3d state dict): report each job's FVD against the original clip "
                         "(city_sender.py:575-589) and save fvd_<idx>.npy; default: the file under models/fvd/, "
                         "fvd_utils/models/fvd/ or benchmark/fvd_utils/models/fvd/ when present, else FVD is skipped")
+    add_yuv_input_flags(p)
+    p.add_argument("--yuv-out", action="store_true",
+                   help="write each job's decoded 30 frames as city_idx<idx>_q<q>_thr<thr>.y4m (8-bit 4:2:0, full-range BT.709) "
+                        "beside its .npy; the frame rate is the --data_yuv file's, else 30")
+    p.add_argument("--yuv-metrics", action="store_true",
+                   help="also save psnr_yuv_frames_<idx>.npy and psnr_yuv_<idx>.npy: the PSNR of the reference's codec benchmark "
+                        "(bench_uvg.py:487,508-509) -- original and decoded clip both go RGB -> 8-bit 4:2:0 -> RGB (bicubic) -> "
+                        "rounded to 8 bits")
     return p
+
+
+YUV_FLAGS = ("data_yuv", "yuv_geometry", "yuv_upsample", "yuv_out", "yuv_metrics")
+
+
+def add_yuv_input_flags(p):
+    p.add_argument("--data_yuv", type=str, default=None,
+                   help="read the clips from a .y4m or raw planar YUV 4:2:0 file (8 or 10 bits) instead of --data_npy: consecutive "
+                        "30-frame clips are videos 0, 1, ...; the frame size must be config.data.image_size")
+    p.add_argument("--yuv-geometry", type=str, default=None,
+                   help="raw .yuv only: WxH[@fps][:bits], e.g. 128x128@30:8 (default: from a _<W>x<H>_<fps>Hz_<bits>bit_ file name)")
+    p.add_argument("--yuv-upsample", choices=["bicubic", "bilinear", "nearest"], default="bicubic",
+                   help="chroma up-sampling of --data_yuv (torch semantics, align_corners=False; the reference uses bicubic)")
+
+
+def parse_args(argv=None, parser=None):
+    """``build_parser().parse_args`` plus what argparse cannot say: --data_yuv replaces --data_npy, it does not join it."""
+    p = parser or build_parser()
+    argv = sys.argv[1:] if argv is None else list(argv)
+    args = p.parse_args(argv)
+    if args.data_yuv and any(a == "--data_npy" or a.startswith("--data_npy=") for a in argv):
+        p.error("--data_yuv replaces --data_npy: pass one of them")
+    if args.yuv_geometry and not args.data_yuv:
+        p.error("--yuv-geometry describes the --data_yuv file: pass --data_yuv")
+    return args
+
+
+def load_yuv_clips(args, image_size, log=print):
+    """The clips of ``--data_yuv`` as the (B, 30, 3, H, W) uint8 array --data_npy would have held, and the file's frame rate."""
+    from . import video_io as V
+    try:
+        v = V.open_video(args.data_yuv, args.yuv_geometry)
+        if (v.height, v.width) != (image_size, image_size):
+            sys.exit(f"--data_yuv {args.data_yuv}: frames are {v.width}x{v.height}, the model's config.data.image_size is "
+                     f"{image_size}; resizing is not built (the reference resizes with ffmpeg / PIL, which cannot be reproduced "
+                     f"here): scale the file to {image_size}x{image_size} first")
+        return V.read_clips(v, upsample=args.yuv_upsample, log=log), v.fps
+    except V.VideoFormatError as e:
+        sys.exit(f"--data_yuv: {e}")
 
 
 def resolve_fvd(args, log=print):
@@ -198,7 +248,7 @@ def save_output(gt, xge, q, thr, idx, output_dir):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     import yaml
     from . import dist as D
     if D.needs_self_launch(args.gpus):      # parent: starts the ranks before any HIP call, relays their exit status
@@ -254,7 +304,8 @@ def main(argv=None):
         with open(os.path.join(vf, "config.yml"), "w") as f:
             yaml.dump(raw, f, default_flow_style=False)
         with open(os.path.join(vf, "args.yml"), "w") as f:
-            yaml.dump(vars(args), f, default_flow_style=False)
+            defaults = vars(build_parser().parse_args([]))      # the YUV flags appear only when used
+            yaml.dump({k: v for k, v in vars(args).items() if k not in YUV_FLAGS or v != defaults[k]}, f, default_flow_style=False)
 
     # ---- weights: rank 0 reads (or synthesises) them, one RCCL broadcast each ----
     sd_d, sd_e = None, {}
@@ -278,7 +329,12 @@ def main(argv=None):
     net = build_score_network(cfg, sd_d, device=device)     # model.arch: unetmore (default, + spade) | unetmorepseudo3d | unet
     models = {q: ElicModel(D.broadcast_state_dict(sd_e.get(q), 0, device, world), device=device) for q in args.q}
 
-    if os.path.exists(args.data_npy):
+    yuv_fps = 30
+    if args.data_yuv:
+        data, yuv_fps = load_yuv_clips(args, cfg.data.image_size, log=lambda m: print(f"[rank {rank}] {m}", flush=True))
+        if args.end_idx >= len(data):
+            sys.exit(f"--data_yuv {args.data_yuv} holds {len(data)} clip(s) of 30 frames; --end_idx {args.end_idx} is beyond them")
+    elif os.path.exists(args.data_npy):
         data = np.load(args.data_npy, mmap_mode="r")
     elif args.synthetic:
         data = synthetic.make_clips(args.end_idx + 1, seed=args.seed)
@@ -294,7 +350,7 @@ def main(argv=None):
     t_start = time.time()
     vids = list(range(args.start_idx + lo, args.start_idx + hi))
 
-    gt_feats, fvd_store = {}, {}
+    gt_feats, fvd_store, yuv_store = {}, {}, {}
 
     def job_fvds(jobs):
         """FVD of each decoded clip against its video's original, as city_sender.py:575-577 computes it: calculate_fvd of
@@ -323,6 +379,12 @@ def main(argv=None):
         g = np.concatenate(list(gt.transpose(0, 2, 3, 1)), axis=1)
         xg = np.concatenate(list(x.transpose(0, 2, 3, 1)), axis=1)
         save_output(g, xg, q, thr, vid, os.path.join(args.output_path, f"output_{vid}"))
+        if args.yuv_out:
+            from . import video_io as V
+            V.write_clip(os.path.join(args.output_path, f"output_{vid}", "city_idx%d_q%d_thr%.2f.y4m" % (vid, q, thr)), x, yuv_fps)
+        if args.yuv_metrics:
+            from . import video_io as V
+            yuv_store.setdefault(vid, []).append(V.psnr_yuv(x, gt))
 
     store = {}
     if args.policy == "mask":
@@ -405,6 +467,9 @@ def main(argv=None):
         np.save(os.path.join(out_root, f"psnr_{vid}.npy"), rd_envelope(bpps, np.mean(np.asarray(ps), 1), True))
         np.save(os.path.join(out_root, f"psnr_frames_{vid}.npy"), np.asarray(ps))
         np.save(os.path.join(out_root, f"bpp_{vid}.npy"), np.asarray(bpps))
+        if vid in yuv_store:     # the codec benchmark's PSNR (bench_uvg.py:487,508-509), laid out as psnr_<idx>.npy
+            np.save(os.path.join(out_root, f"psnr_yuv_{vid}.npy"), rd_envelope(bpps, np.mean(np.asarray(yuv_store[vid]), 1), True))
+            np.save(os.path.join(out_root, f"psnr_yuv_frames_{vid}.npy"), np.asarray(yuv_store[vid]))
         if vid in fvd_store:     # reference name fvd_<idx>.npy: RD envelope [bpp; FVD], lower is better; raw values beside it
             np.save(os.path.join(out_root, f"fvd_{vid}.npy"), rd_envelope(bpps, np.asarray(fvd_store[vid]), False))
             np.save(os.path.join(out_root, f"fvd_values_{vid}.npy"), np.asarray(fvd_store[vid]))

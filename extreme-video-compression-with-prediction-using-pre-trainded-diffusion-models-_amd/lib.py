@@ -176,6 +176,8 @@ HIP_SYMBOLS = {
     "evc_elic_scatter_symbols_f32": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     "evc_elic_quantize_f32": (c_int, [c_void_p, c_int, c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p]),
     "evc_noise_normal_f32": (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_ulonglong, c_uint, c_int, c_void_p]),
+    "evc_yuv420_to_rgb": (c_int, [c_void_p] + [c_longlong] * 6 + [c_int] * 5 + [c_void_p, c_int, c_void_p]),
+    "evc_rgb_to_yuv420": (c_int, [c_void_p, c_void_p] + [c_longlong] * 6 + [c_int] * 4 + [c_void_p, c_void_p]),
 }
 
 RANS_SYMBOLS = {
@@ -1045,6 +1047,50 @@ def noise_normal(keys, shape, seed, step, raw=False, out=None):
     _check(hip_lib().evc_noise_normal_f32(fptr(out), ptr(keys), B, n, int(seed) & (2 ** 64 - 1), int(step), int(bool(raw)),
                                           stream_ptr()), "evc_noise_normal_f32")
     return out.view(torch.int32) if raw else out
+
+
+# ---- YUV 4:2:0 <-> RGB (include/evc_hip.h evc_yuv420_to_rgb / evc_rgb_to_yuv420) ------------------------------------
+YUV_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}
+
+
+def yuv420_frame_bytes(H, W, bits=8):
+    """Bytes of one planar 4:2:0 frame: Y, then U, then V."""
+    return H * W * (2 if bits > 8 else 1) * 3 // 2
+
+
+def _yuv_layout(H, W, bits, first, stride, offsets):
+    luma = H * W * (2 if bits > 8 else 1)
+    off = (0, luma, luma + luma // 4) if offsets is None else tuple(int(o) for o in offsets)
+    return int(first), int(luma * 3 // 2 if stride is None else stride), off
+
+
+def yuv420_to_rgb(buf, N, H, W, bits=8, mode="bicubic", first=0, stride=None, offsets=None, dtype=torch.float32, out=None):
+    """buf: 1-D uint8 device tensor holding N planar 4:2:0 frames, frame n at byte ``first + n * stride`` (default: packed),
+    its planes at ``offsets`` = (Y, U, V) from there (default: Y, U, V back to back) -> (N, 3, H, W) RGB, float32 unclamped or
+    uint8 = rint(clamp(rgb * 255))."""
+    assert buf.dtype == torch.uint8 and buf.dim() == 1 and dtype in (torch.float32, torch.uint8)
+    first, stride, off = _yuv_layout(H, W, bits, first, stride, offsets)
+    if out is None:
+        out = torch.empty((N, 3, H, W), device=buf.device, dtype=dtype)
+    assert out.dtype == dtype and tuple(out.shape) == (N, 3, H, W)
+    _check(hip_lib().evc_yuv420_to_rgb(ptr(buf), buf.numel(), first, stride, off[0], off[1], off[2], N, H, W, bits,
+                                       YUV_MODES[mode], ptr(out), int(dtype == torch.uint8), stream_ptr()), "evc_yuv420_to_rgb")
+    return out
+
+
+def rgb_to_yuv420(x, events, bits=8, buf=None, first=0, stride=None, offsets=None):
+    """x: (N, 3, H, W) float32 in [0, 1] -> the 1-D uint8 device tensor of its planar 4:2:0 samples (``buf``, ``first``,
+    ``stride``, ``offsets`` as in ``yuv420_to_rgb``; default: a new packed buffer).  events: int32 device word (1 element); a
+    non-finite pixel writes 0 and ORs RANGE_NONFINITE into it."""
+    assert x.dim() == 4 and x.shape[1] == 3 and events.dtype == torch.int32 and events.numel() == 1
+    N, _, H, W = x.shape
+    first, stride, off = _yuv_layout(H, W, bits, first, stride, offsets)
+    if buf is None:
+        buf = torch.empty(first + N * stride, device=x.device, dtype=torch.uint8)
+    assert buf.dtype == torch.uint8 and buf.dim() == 1
+    _check(hip_lib().evc_rgb_to_yuv420(fptr(x.contiguous()), ptr(buf), buf.numel(), first, stride, off[0], off[1], off[2], N, H, W,
+                                       bits, ptr(events), stream_ptr()), "evc_rgb_to_yuv420")
+    return buf
 
 
 def gate_residual(a, b, x, out=None):

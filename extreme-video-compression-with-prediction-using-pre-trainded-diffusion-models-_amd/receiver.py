@@ -115,12 +115,17 @@ def build_parser():
                         "it (streams of a city_sender.py --share-generations sweep share most of their rounds); --batch then "
                         "counts states per launch")
     p.add_argument("--data_npy", type=str, default="city_bonn.npy", help="original clips: when present, per-job PSNR is printed")
+    from .cli import add_yuv_input_flags
+    add_yuv_input_flags(p)       # --data_yuv: the original clips from a Y4M / raw 4:2:0 file instead (city_sender.py's flags)
+    p.add_argument("--yuv", action="store_true",
+                   help="also write decoded_v<vid>_q<q>_thr<thr>.y4m (8-bit 4:2:0, full-range BT.709) beside each .npy")
+    p.add_argument("--fps", type=str, default="30", help="--yuv: frame rate of the written files (30, 29.97 or 30000/1001)")
     return p
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
     from . import ckpt, cli, config as C, lib as L, synthetic
+    args = cli.parse_args(argv, build_parser())
     from .elic import ElicModel
     from .scorenet import build_score_network
     paths = args.paths or cli.DEFAULT_PATHS
@@ -154,7 +159,10 @@ def main(argv=None):
     if args.share_generations:
         log(f"shared generations: {stats.get('samples', 0)} sample-rounds generated for {stats.get('job_rounds', 0)} job-rounds "
             f"served, {stats.get('key_frames_decoded', 0)} key frames decoded")
-    data = np.load(args.data_npy, mmap_mode="r") if os.path.exists(args.data_npy) else None
+    if args.data_yuv:
+        data, _ = cli.load_yuv_clips(args, cfg.data.image_size, log=log)
+    else:
+        data = np.load(args.data_npy, mmap_mode="r") if os.path.exists(args.data_npy) else None
     os.makedirs(args.output_path, exist_ok=True)
     note = cli.recovery_note(decoders[0])
     mismatches = 0
@@ -163,6 +171,9 @@ def main(argv=None):
         cli.check_numerics(x, f"{os.path.basename(path)}", note)
         x = x.cpu().numpy()
         np.save(os.path.join(args.output_path, f"decoded_{name}.npy"), x)
+        if args.yuv:
+            from . import video_io as V
+            V.write_clip(os.path.join(args.output_path, f"decoded_{name}.y4m"), x, args.fps)
         line = f"{os.path.basename(path)}: {job['frames']} frames, {int(job['d'].sum())} key frames, " \
                f"{container.payload_bits(job['key_strings'])} bits, {job['sampler']}-{job['subsample']}"
         if data is not None:

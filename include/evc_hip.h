@@ -478,6 +478,36 @@ int evc_gdn_f32(const float* x, const void* gamma_packed, int arith, const float
 int evc_noise_normal_f32(float* out, const unsigned* keys, int B, long long n, unsigned long long seed, unsigned step,
                          int raw, void* stream);
 
+/* ---- YUV 4:2:0 <-> RGB: the video file boundary (csrc/yuv.hip) ------------------------------
+ * The conventions of the reference's codec benchmark: 8-bit (or 10-bit, little-endian 16-bit samples) planar 4:2:0, full-range
+ * BT.709, chroma sited at the centre of its 2x2 luma block.  Both calls describe the samples as ONE device byte buffer of
+ * `bytes` bytes: frame n starts at byte first + n * frame_stride, its Y / U / V planes at off_y / off_u / off_v from there
+ * (Y: H x W samples, U and V: H/2 x W/2, rows contiguous), so an uploaded piece of a raw .yuv file or of a Y4M file (a
+ * "FRAME\n" marker before every frame) is converted where it lies.  No alignment is asked of the offsets.  N <= 65535 frames
+ * per launch, H and W even and >= 2, bits 8 or 10, every plane inside the buffer: anything else returns EVC_EINVAL before a launch.
+ *   evc_yuv420_to_rgb   ycbcr2rgb(yuv_420_to_444(frame, mode).true_divide(max_val)), benchmark/fvd_utils/bench_uvg.py:479 with
+ *                       yuv_420_to_444 (:345-382; benchmark/transform.py:110-147) and ycbcr2rgb (:384-402; transform.py:47-65):
+ *                       the raw chroma samples are up-sampled x2 as torch's F.interpolate does (EVC_YUV_NEAREST, _BILINEAR,
+ *                       _BICUBIC; align_corners=False, border indices clamped, bicubic A = -0.75), all three planes divided by
+ *                       maxv = 2^bits - 1, then r = y + (2 - 2 Kr)(cr - 0.5), b = y + (2 - 2 Kb)(cb - 0.5), g = (y - Kr r - Kb b) /
+ *                       Kg with K = 0.2126 / 0.7152 / 0.0722.  out: (N, 3, H, W) NCHW; out_u8 == 0: float32, unclamped (what
+ *                       the reference feeds LPIPS and FVD); out_u8 != 0: uint8 = rint(clamp(rgb * 255, 0, 255)), round half to
+ *                       even (bench_uvg.py:487; the --data_npy convention).
+ *   evc_rgb_to_yuv420   rgb (N, 3, H, W) float32 in [0, 1] -> samples: rgb2ycbcr (transform.py:26-44), chroma = the 2x2 average
+ *                       (yuv_444_to_420, :78-107, avg_pool), sample = rint(clamp(v * maxv, 0, maxv)), round half to even.  A
+ *                       pixel with a NaN or an infinity writes 0 to its luma sample and to the chroma samples of its 2x2 block
+ *                       and ORs EVC_RANGE_NONFINITE into *events (a device word, never NULL); nothing else is saturated
+ *                       beyond the clamp. */
+#define EVC_YUV_NEAREST 0
+#define EVC_YUV_BILINEAR 1
+#define EVC_YUV_BICUBIC 2
+int evc_yuv420_to_rgb(const unsigned char* src, long long src_bytes, long long first, long long frame_stride, long long off_y,
+                      long long off_u, long long off_v, int N, int H, int W, int bits, int mode, void* out, int out_u8,
+                      void* stream);
+int evc_rgb_to_yuv420(const float* rgb, unsigned char* dst, long long dst_bytes, long long first, long long frame_stride,
+                      long long off_y, long long off_u, long long off_v, int N, int H, int W, int bits, unsigned* events,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
