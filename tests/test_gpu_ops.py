@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_ledger as ledger
 from conftest import golden, rnd
 
 pytestmark = pytest.mark.gpu
@@ -46,6 +47,26 @@ def nchw(x):
 
 def silu_affine(x, a, s):
     return F.silu(x * a[:, :, None, None] + s[:, :, None, None])
+
+
+def profiled(L, call):
+    """-> (result of ``call()``, the ``lib.CONV_PROFILE`` records of the convolutions it launched)."""
+    prof = []
+    L.CONV_PROFILE = prof
+    try:
+        r = call()
+    finally:
+        L.CONV_PROFILE = None
+    return r, prof
+
+
+def assert_ledger_class(test, rec, *launch):
+    """The launch recorded in ``rec`` ran on the kernel, and with the split-K slabs, that tests/conv_ledger.py NAMED states for
+    this case of ``test`` (the CPU test tests/test_conv_ledger_host.py keeps that table equal to the planner)."""
+    cls = ledger.named_class(test, *launch)
+    assert rec["kernel"] == cls[0], (rec["kernel"], cls)
+    assert rec["split"] == (cls[1] != "none"), (rec["split"], cls)
+    return cls
 
 
 @pytest.mark.parametrize("B,H,W,Ci,Co,K", [(2, 16, 16, 192, 192, 3), (1, 5, 7, 32, 48, 3), (2, 8, 8, 64, 15, 3),
@@ -119,19 +140,23 @@ def test_conv_fused_epilogue_moments_match_separate_pass(L, arith):
 
 
 @pytest.mark.parametrize("B,H,W,C0,C1,Co,splits", [
-    (3, 8, 8, 32, 16, 192, 0),      # W = 8: a 128-pixel tile spans two images; M = 192 leaves a partial last tile
-    (3, 8, 8, 32, 16, 192, 3),      # same through split-K (splits cover whole kernel rows)
-    (2, 16, 16, 48, 0, 192, 2),     # W = 16: eight image rows per tile
-    (2, 32, 32, 16, 32, 64, 0),     # W = 32, Co = 64 (one 64-wide N tile), concat crossing a chunk boundary
-    (1, 64, 64, 16, 0, 128, 0),     # W = 64: two image rows per tile, 128-wide N tile
-    (1, 128, 128, 16, 16, 192, 0),  # W = 128: one image row per tile
-    (1, 4, 4, 16, 0, 192, 0),       # W = 4: 32 image rows per tile, M = 16 (mostly padding)
-    (8, 128, 128, 16, 16, 64, 0),   # 512 tiles of 256 pixels: the 8-wave / 256-pixel form of the kernel
+    # what each shape runs on today (tests/conv_ledger.py NAMED; asserted below) -- bf16x6 / f16x3:
+    (3, 8, 8, 32, 16, 192, 0),      # W = 8, M = 192: 64-pixel tiles of conv_split_kernel / conv_splitn_kernel, z-split
+    (3, 8, 8, 32, 16, 192, 3),      # the same with the 3-way split asked for
+    (2, 16, 16, 48, 0, 192, 2),     # W = 16: 64-pixel tiles, 2-way z-split
+    (2, 32, 32, 16, 32, 64, 0),     # W = 32, Co = 64 (one 64-wide N tile), concat crossing a chunk boundary: 64-pixel tiles, z-split
+    (1, 64, 64, 16, 0, 128, 0),     # W = 64, 128-wide N tile: 64-pixel tiles, unsplit
+    (1, 128, 128, 16, 16, 192, 0),  # W = 128: the row-reuse kernel with a z-split (bf16x6); 64-pixel tiles, unsplit (f16x3)
+    (1, 4, 4, 16, 0, 192, 0),       # W = 4, M = 16: one partial 64-pixel tile
+    (8, 128, 128, 16, 16, 64, 0),   # 512 tiles of 256 pixels: the 8-wave / 256-pixel form of the row-reuse kernel (both)
 ])
 def test_conv3x3_row_reuse_shapes(L, split_arith, B, H, W, C0, C1, Co, splits):
-    """3x3 convolutions on tiles made of whole image rows run on the row-reuse kernel (activation staged once per
-    kernel row, taps read at shifted LDS offsets, zero halo pixels for the horizontal borders): every image width
-    it supports, tiles spanning images, partial tiles, concat sources, GroupNorm+SiLU on load, split-K."""
+    """3x3 convolutions at the image widths of the row-reuse kernel, small grids: concat sources, GroupNorm + SiLU on load,
+    bias, residual, split-K, and the same shapes with a plain input.  The planner gives most of these grids the 64-pixel
+    tiles of conv_split_kernel / conv_splitn_kernel (see the table); the kernel and split of every case is asserted.  The
+    row-reuse kernel itself (activation staged once per kernel row, taps read at shifted LDS offsets, zero halo pixels for the
+    horizontal borders) at every width it supports -- W = 4 ... 128, tiles spanning images, partial last tile, z-split and
+    K-split tail, both split arithmetics -- is tests/test_gpu_conv_ledger.py, entries rr<...> of tests/conv_ledger.py CASES."""
     x0 = rnd(50, B, C0, H, W).cuda()
     x1 = rnd(51, B, C1, H, W).cuda() if C1 else None
     C = C0 + C1
@@ -140,17 +165,22 @@ def test_conv3x3_row_reuse_shapes(L, split_arith, B, H, W, C0, C1, Co, splits):
     b, res = rnd(55, Co).cuda(), rnd(56, B, Co, H, W).cuda()
     xin = torch.cat([x0, x1], 1).cpu() if C1 else x0.cpu()
     ref = (F.conv2d(silu_affine(xin, a.cpu(), s.cpu()), w.cpu(), b.cpu(), padding=1) + res.cpu()) * 0.5
-    out = L.conv2d_nhwc(nhwc(x0), L.conv_pack_weights(w, split_arith), Co, 3, 3, bias=b,
-                        src1=None if x1 is None else nhwc(x1), coef=(a, s), act_in=L.ACT_SILU, res=nhwc(res),
-                        out_scale=0.5, splits=splits)
+    out, prof = profiled(L, lambda: L.conv2d_nhwc(nhwc(x0), L.conv_pack_weights(w, split_arith), Co, 3, 3, bias=b,
+                                                  src1=None if x1 is None else nhwc(x1), coef=(a, s), act_in=L.ACT_SILU,
+                                                  res=nhwc(res), out_scale=0.5, splits=splits))
+    cls = assert_ledger_class("test_conv3x3_row_reuse_shapes", prof[0], B, H, W, C0, C1, Co, 3, split_arith, 1, L.ACT_SILU,
+                              splits, 0)
     assert rel(nchw(out), ref) < 1e-5
     # plain (no transform) input through the same kernel
     ref2 = F.conv2d(xin, w.cpu(), None, padding=1)
-    out2 = L.conv2d_nhwc(nhwc(x0), L.conv_pack_weights(w, split_arith), Co, 3, 3,
-                         src1=None if x1 is None else nhwc(x1), splits=splits)
+    out2, prof = profiled(L, lambda: L.conv2d_nhwc(nhwc(x0), L.conv_pack_weights(w, split_arith), Co, 3, 3,
+                                                   src1=None if x1 is None else nhwc(x1), splits=splits))
+    assert prof[0]["kernel"] == cls[0][:-2] + "0>", (prof[0]["kernel"], cls)       # same instance, on-load mode 0
     assert rel(nchw(out2), ref2) < 1e-5
 
 
+# bf16x6: the row-reuse kernel with a K-split tail in all three; f16x3: conv_wide_kernel with a K-split tail in the first two
+# (the third, Co = 128, stays on the row-reuse kernel) -- asserted below
 @pytest.mark.parametrize("B,H,W,C0,C1,Co", [(9, 64, 64, 64, 32, 384),     # 576 workgroups: one round + 32 tiles x 2 n-tiles split 2 ways
                                              (5, 128, 128, 96, 0, 192),    # 640 workgroups: one round + 128 tiles split 2 ways
                                              (5, 128, 128, 48, 48, 128)])  # 128-wide N tile (two 32-column MFMA tiles per wave)
@@ -158,7 +188,8 @@ def test_conv3x3_k_split_tail(L, split_arith, B, H, W, C0, C1, Co):
     """Unsplit grids of 1.x rounds: the pixel tiles of the partial last round are split along K inside the same launch
     (conv_tile_cfg, option "tail_split"), their slabs combined by a second kernel over the tail's rows only.  Outputs,
     fused moments (two producers: epilogue and combine) and the untouched main tiles against torch fp32 and against
-    the same launch with the tail switched off."""
+    the same launch with the tail switched off.  Every case gets a tail; which kernel carries it is asserted (NAMED of
+    tests/conv_ledger.py).  The row-reuse tails of the f16x3 arithmetic at Co = 192 and Co = 15 are CASES of the ledger."""
     x0 = rnd(60, B, C0, H, W).cuda()
     x1 = rnd(61, B, C1, H, W).cuda() if C1 else None
     C = C0 + C1
@@ -169,7 +200,9 @@ def test_conv3x3_k_split_tail(L, split_arith, B, H, W, C0, C1, Co):
     kw = dict(bias=b, src1=None if x1 is None else nhwc(x1), coef=(a, s), act_in=L.ACT_SILU, res=nhwc(res), out_scale=0.5)
     assert L.conv_workspace_bytes(B, H, W, C, Co, 3, 3, arith=split_arith) > 0          # the tail is in use ...
     assert L.conv_workspace_bytes(B, H, W, C, Co, 3, 3, arith=split_arith) < B * H * W * Co * 4   # ... and only the tail has slabs
-    out, st = L.conv2d_nhwc(nhwc(x0), wp, Co, 3, 3, want_stats=True, **kw)
+    (out, st), prof = profiled(L, lambda: L.conv2d_nhwc(nhwc(x0), wp, Co, 3, 3, want_stats=True, **kw))
+    cls = assert_ledger_class("test_conv3x3_k_split_tail", prof[0], B, H, W, C0, C1, Co, 3, split_arith, 1, L.ACT_SILU, 0, 0)
+    assert cls[1] == "tail"
     L.conv_set_option("tail_split", 0)
     try:
         base, st0 = L.conv2d_nhwc(nhwc(x0), wp, Co, 3, 3, want_stats=True, splits=1, **kw)
@@ -183,16 +216,18 @@ def test_conv3x3_k_split_tail(L, split_arith, B, H, W, C0, C1, Co):
 
 
 @pytest.mark.parametrize("B,H,W,C0,C1,Co,K,splits", [
-    (2, 32, 32, 32, 16, 192, 3, 2),     # row-reuse kernel, blockIdx.z splits
-    (3, 8, 8, 64, 0, 192, 3, 4),        # M = 192: a partial last pixel tile
+    (2, 32, 32, 32, 16, 192, 3, 2),     # 64-pixel tiles (all three arithmetics), blockIdx.z splits
+    (3, 8, 8, 64, 0, 192, 3, 4),        # M = 192: 64-pixel tiles, three full ones; 4 z-splits
     (2, 16, 16, 96, 32, 384, 1, 3),     # 1x1 filter: the simple-schedule kernel, two channel tiles
-    (9, 64, 64, 32, 0, 192, 3, 0),      # automatic choice on a mid-size grid
-    (5, 128, 128, 16, 16, 192, 3, 0),   # 640 tiles: one round + a K-split TAIL
+    (9, 64, 64, 32, 0, 192, 3, 0),      # automatic choice on a mid-size grid: f32 z-split, the row-reuse kernel unsplit
+    (5, 128, 128, 16, 16, 192, 3, 0),   # 640 tiles of 18 K-steps, too few for a K-split tail: unsplit (f16x3: conv_wide_kernel)
 ])
 def test_conv_split_k_is_deterministic_and_matches_unsplit(L, arith, B, H, W, C0, C1, Co, K, splits):
-    """Split-K launches (blockIdx.z splits and the K-split tail, partial sums to slabs + the combine kernel that adds them
-    in split order): against torch, against the same convolution forced unsplit (same values up to summation order), fused
-    moments, and bitwise run-to-run determinism."""
+    """Split-K launches (blockIdx.z splits, partial sums to slabs + the combine kernel that adds them in split order) and the
+    automatic choice on two larger grids: against torch, against the same convolution forced unsplit (same values up to
+    summation order), fused moments, and bitwise run-to-run determinism.  The kernel and split kind of every case is asserted
+    (NAMED of tests/conv_ledger.py).  The z-split of the row-reuse kernel and a genuine K-split tail per arithmetic, with the
+    same determinism check, are CASES of the ledger (tests/test_gpu_conv_ledger.py)."""
     x0 = rnd(50, B, C0, H, W).cuda()
     x1 = rnd(51, B, C1, H, W).cuda() if C1 else None
     C = C0 + C1
@@ -204,7 +239,9 @@ def test_conv_split_k_is_deterministic_and_matches_unsplit(L, arith, B, H, W, C0
     wp = L.conv_pack_weights(w, arith)
     kw = dict(bias=b, src1=None if x1 is None else nhwc(x1), coef=(a, s), act_in=L.ACT_SILU, res=nhwc(res), out_scale=0.5,
               want_stats=True)
-    out, st = L.conv2d_nhwc(nhwc(x0), wp, Co, K, K, splits=splits, **kw)
+    (out, st), prof = profiled(L, lambda: L.conv2d_nhwc(nhwc(x0), wp, Co, K, K, splits=splits, **kw))
+    assert_ledger_class("test_conv_split_k_is_deterministic_and_matches_unsplit", prof[0], B, H, W, C0, C1, Co, K, arith, 1,
+                        L.ACT_SILU, splits, 0)
     assert rel(nchw(out), ref) < 2e-5
     o = out.double().reshape(B, H * W, Co)
     assert rel(st.double().sum(1).float(), torch.stack([o.sum(1), (o * o).sum(1)], -1).float()) < 1e-5
