@@ -18,6 +18,8 @@ job stream per reported job (container format 3; format 4 with ``--batch-invaria
 ``--data_yuv FILE`` reads the clips from a Y4M or raw planar YUV 4:2:0 file instead of ``--data_npy`` (video_io.py: the
 reference's benchmark conventions, converted by the HIP kernels of csrc/yuv.hip), ``--yuv-out`` writes each job's decoded clip
 as ``.y4m`` and ``--yuv-metrics`` adds the PSNR of the reference's codec benchmark.
+``--entropy-estimation`` (a reference flag) reports every key frame's rate as the sum of -log2(likelihood), computed on the GPU
+(``ElicModel.estimate``) instead of the length of range-coded strings: same frames, fractional bits.
 """
 import argparse
 import os
@@ -49,7 +51,11 @@ def build_parser():
     p.add_argument("-c", "--entropy-coder", choices=["ans"], default="ans", help="entropy coder")
     p.add_argument("--cuda", default=True, help="enable the GPU (always on: there is no CPU path)")
     p.add_argument("--plot", default=True, help="kept for compatibility (RD plots are out of scope)")
-    p.add_argument("--entropy-estimation", action="store_true")
+    p.add_argument("--entropy-estimation", action="store_true",
+                   help="key-frame rate from the likelihoods (sum of -log2, TestModel.inference of the reference) instead of the "
+                        "length of range-coded strings: same decoded frames, fractional bits, no host coder on the key-frame path. "
+                        "Needs the entropy bottleneck's density parameters in the ELIC checkpoints; writes no strings, so it does "
+                        "not combine with --bitstream-dir")
     p.add_argument("-p", "--path", dest="paths", type=str, nargs="+", default=DEFAULT_PATHS, help="ELIC checkpoints")
     p.add_argument("--patch", type=int, default=64, help="padding patch size")
     p.add_argument("--start_idx", type=int, default=0, help="Start video index")
@@ -249,6 +255,9 @@ def save_output(gt, xge, q, thr, idx, output_dir):
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.entropy_estimation and args.bitstream_dir:
+        sys.exit("--entropy-estimation with --bitstream-dir: an estimated rate comes without coded strings, so there is nothing "
+                 "to write into a bitstream; drop one of the two")
     import yaml
     from . import dist as D
     if D.needs_self_launch(args.gpus):      # parent: starts the ranks before any HIP call, relays their exit status
@@ -322,7 +331,8 @@ def main(argv=None):
             if os.path.exists(pth):
                 sd_e[q] = ckpt.load_elic_state_dict(pth)
             elif args.synthetic:
-                sd_e[q] = synthetic.elic_state_dict(q)
+                # the same weights either way; estimation also needs the density behind the bottleneck's tables
+                sd_e[q] = synthetic.elic_state_dict_with_density(q) if args.entropy_estimation else synthetic.elic_state_dict(q)
             else:
                 sys.exit(f"missing {pth} (pass --synthetic)")
     sd_d = D.broadcast_state_dict(sd_d, 0, device, world)
@@ -400,10 +410,16 @@ def main(argv=None):
             for b0 in range(0, len(vids), max(1, args.batch)):
                 chunk = vids[b0:b0 + max(1, args.batch)]
                 gt = torch.from_numpy(np.stack([np.asarray(data[v], dtype=np.float32) / 255.0 for v in chunk]))
-                keys, shape = [], None
+                keys, shape, est_bits = [], None, []
+                key_frames = [] if args.entropy_estimation else None
                 for f in (0, 1):                                   # key frames (city_sender.py:521-524), batched
                     pad = (-gt.shape[-1]) % args.patch, (-gt.shape[-2]) % args.patch
                     xk = torch.nn.functional.pad(gt[:, f], (0, pad[0], 0, pad[1]))
+                    if args.entropy_estimation:                    # no strings: the decoder is handed the frames themselves
+                        est = model.estimate(xk.to(device))
+                        key_frames.append(est["x_hat"])
+                        est_bits.append((est["bits_y"] + est["bits_z"]).tolist())
+                        continue
                     enc = model.compress(xk.to(device))
                     keys.append(enc["strings"]); shape = enc["shape"]
                 d_rx, keys_rx, shape_rx = mask, keys, shape
@@ -415,12 +431,13 @@ def main(argv=None):
                         fh.write(container.pack(mask, keys, shape, codec=model.codec_tag()))
                     with open(path, "rb") as fh:          # refuses a stream coded under another arithmetic
                         d_rx, keys_rx, shape_rx = container.unpack(fh.read(), expect_codec=model.codec_tag())
-                frames = dec.decode(d_rx, keys_rx, shape_rx, generator=gen)[..., :gt.shape[-2], :gt.shape[-1]]
+                frames = dec.decode(d_rx, keys_rx, shape_rx, generator=gen, key_frames=key_frames)[..., :gt.shape[-2], :gt.shape[-1]]
                 check_numerics(frames, f"videos {chunk[0]}..{chunk[-1]} q{q}", recovery_note(dec))
                 x_all = frames.cpu().numpy()
                 fvds = job_fvds([(vid, x_all[j], gt[j].numpy()) for j, vid in enumerate(chunk)])
                 for j, vid in enumerate(chunk):
-                    bits = [count_bits([[[[p[j]] for p in sl] for sl in k[0]], [k[1][j]]]) for k in keys]
+                    bits = [b[j] for b in est_bits] if args.entropy_estimation else \
+                        [count_bits([[[[p[j]] for p in sl] for sl in k[0]], [k[1][j]]]) for k in keys]
                     report(vid, q, 0.0, x_all[j], gt[j].numpy(), bits, mask, store, fvds[j])
     else:
         # city_sender.py:495-607 batched (policy.py): every (video, q, threshold) job of this rank advances in lockstep,
@@ -433,7 +450,7 @@ def main(argv=None):
         shared = dict(noise_streams="group", share=True, stats={}) if args.share_generations else {}
         res = P.run_policy(dec, models, clips, args.q, thresholds, metric, patch=args.patch, max_batch=args.policy_batch,
                            seed=args.seed, device=device, bpp_limit=args.bpp_limit, log=lambda m: print(f"[rank {rank}] {m}", flush=True),
-                           noise=args.noise, batch_invariant=args.batch_invariant, **shared)
+                           noise=args.noise, batch_invariant=args.batch_invariant, estimate=args.entropy_estimation, **shared)
         if shared:
             st = shared["stats"]
             print(f"[rank {rank}] shared generations: {sum(st['states'])} sample-rounds generated for {sum(st['jobs_served'])} "

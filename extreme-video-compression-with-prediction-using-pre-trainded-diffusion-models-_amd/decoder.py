@@ -178,21 +178,28 @@ class ClipDecoder:
         return self._stream_pool[:n]
 
     @torch.no_grad()
-    def decode(self, d, key_strings, shape, frames=30, noise_fn=None, generator=None):
+    def decode(self, d, key_strings, shape, frames=30, noise_fn=None, generator=None, key_frames=None):
         """d: (frames,) 0/1 mask shared by the batch; key_strings: list over key-frame positions (in order) of
-        ``[y_strings, z_strings]`` for the whole batch.  Returns (B, frames, 3, H, W) float32 on the device."""
+        ``[y_strings, z_strings]`` for the whole batch.  Returns (B, frames, 3, H, W) float32 on the device.
+        ``key_frames``: the decoded key frames themselves, one (B, 3, H, W) device tensor per key-frame position, for a sender
+        that estimated its rate and has no strings (``ElicModel.estimate``); ``key_strings`` and ``shape`` are then not read."""
         d = np.asarray(d).reshape(-1)
         out = []
         k = 0
         t = 0
         n_key = int(d[:frames].sum())
-        assert len(key_strings) >= n_key, "not enough key-frame bitstreams for the mask"
+        assert len(key_frames if key_frames is not None else key_strings) >= n_key, "not enough key frames for the mask"
         while t < frames:
             if d[t] == 1:
                 # decode every consecutive key frame of this run in one batched ELIC call
                 run = 0
                 while t + run < frames and d[t + run] == 1:
                     run += 1
+                if key_frames is not None:
+                    out.append(torch.stack(list(key_frames[k:k + run]), 1))
+                    k += run
+                    t += run
+                    continue
                 ys = [[[s for f in range(run) for s in key_strings[k + f][0][i][p]] for p in range(2)]
                       for i in range(len(key_strings[k][0]))]
                 zs = [s for f in range(run) for s in key_strings[k + f][1]]

@@ -15,13 +15,15 @@ Every convolution runs through ``evc_conv2d_nhwc_f32`` (NHWC, f32 matrix cores):
 * the concat feeding ParamAggregation is never materialised: context + channel-conditional outputs are
   written side by side into one buffer, the hyper-prior output is the second conv source;
 * entropy coding: scale -> CDF index, mean gather and symbol scatter are GPU kernels; only int32
-  indexes / symbols cross to the host range coder (libevc_rans.so), per (slice, pass) as in the reference.
+  indexes / symbols cross to the host range coder (libevc_rans.so), per (slice, pass) as in the reference;
+* rate estimation (``estimate``, the reference's ``TestModel.inference``, Network.py:534-640): quantisation, likelihoods and
+  the bit sums are GPU kernels (csrc/rate.hip); nothing crosses to the host but the per-frame totals at the end.
 """
 import numpy as np
 import torch
 
 from . import lib as L
-from .entropy import EntropyBottleneckCodec, Tables
+from .entropy import (DensityParametersMissing, EntropyBottleneckCodec, Tables, density_from_state_dict, pack_density)
 
 GROUPS = [0, 16, 16, 32, 64, 192]   # Network.py:87
 ONE = np.ones((1, 1), dtype=np.float32)
@@ -84,6 +86,21 @@ class ElicModel:
         self.scale_table = sd["gaussian_conditional.scale_table"].detach().float().to(self.device).contiguous()
         self.eb = EntropyBottleneckCodec(Tables.from_state_dict(sd, "entropy_bottleneck"),
                                          sd["entropy_bottleneck.quantiles"][:, 0, 1].detach().float().cpu().numpy())
+        self.medians = torch.from_numpy(self.eb.medians.copy()).to(self.device)
+        self._load_density(sd)
+
+    def _load_density(self, sd):
+        """The density behind the bottleneck's tables: optional (coding reads the tables only), ``estimate`` needs it."""
+        raw, self.density_missing = density_from_state_dict(sd, "entropy_bottleneck")
+        self.density = None if raw is None else pack_density(*raw).to(self.device)
+
+    def _require_density(self):
+        if self.density is None:
+            raise DensityParametersMissing(
+                "ElicModel.estimate needs the entropy bottleneck's density, which this checkpoint does not hold (missing: "
+                + ", ".join(self.density_missing) + "; later compressai releases spell them entropy_bottleneck.matrices.<i> / "
+                "biases.<i> / factors.<i>, which is accepted too).  The model still compresses and decompresses: those read "
+                "the quantised tables only")
 
     def codec_tag(self):
         """(convolution arithmetic, revision) the entropy parameters of this model are computed with."""
@@ -174,9 +191,11 @@ class ElicModel:
         return self._conv("h_s.4", x)               # (B, H, W, 2M) = [means | scales]
 
     # ---- the slice / checkerboard loop shared by encode and decode -------------------------------
-    def _slice_loop(self, hs, y_hat, code_pass):
+    def _slice_loop(self, hs, y_hat, code_pass, rate_pass=None):
         """hs: (B,H,W,2M) hyper-prior output; y_hat: (B,H,W,M) zero-initialised, filled in place.
-        ``code_pass(i, parity, c0, g, idx, means)`` returns the int32 symbols (B,g,H,W/2) on the device."""
+        ``code_pass(i, parity, c0, g, idx, means)`` returns the int32 symbols (B,g,H,W/2) on the device.
+        ``rate_pass(k, i, parity, c0, g, ms)`` (k = pass number 0..9), when given, takes the place of gather + ``code_pass`` +
+        scatter: it fills the pass's sites of y_hat itself from ms = [means | scales] (``estimate``)."""
         B, H, W, _ = hs.shape
         c0 = 0
         prev = None
@@ -196,6 +215,9 @@ class ElicModel:
                 t = self._conv(f"ParamAggregation.{i}.0", pa_in, src1=hs, act_out=L.ACT_RELU)
                 t = self._conv(f"ParamAggregation.{i}.2", t, act_out=L.ACT_RELU)
                 ms = self._conv(f"ParamAggregation.{i}.4", t)                    # (B,H,W,2g) = [means | scales]
+                if rate_pass is not None:
+                    rate_pass(2 * i + parity, i, parity, c0, g, ms)
+                    continue
                 idx, means = L.elic_gather_params(ms, 0, g, g, parity, self.scale_table)
                 sym = code_pass(i, parity, c0, g, idx, means)
                 L.elic_scatter_symbols(sym, means, y_hat, c0, parity)
@@ -257,6 +279,43 @@ class ElicModel:
             out.update(y=y.permute(0, 3, 1, 2).contiguous(), y_hat=y_hat.permute(0, 3, 1, 2).contiguous())
         return out
 
+    @torch.no_grad()
+    def estimate(self, x, return_latents=False):
+        """TestModel.inference (Network.py:534-640): the decoded frames and the rate, without an entropy coder.
+        x: (B, 3, H, W) in [0, 1], H and W multiples of 64 -> {"x_hat", "bits_y" (B,) float64, "bits_z" (B,) float64, "shape"}:
+        per frame the sum of -log2(likelihood) over y and over z; ``shape`` as ``compress`` reports it.  x_hat (and y_hat, z_hat) are bit for bit those of
+        ``decompress(compress(x))``: the same quantised values go through the same launches.  Nothing is read back before the
+        per-pass totals at the end (one copy); the host adds a frame's ten pass totals in float64 in slice / parity order."""
+        self._require_density()
+        x = x.to(self.device, torch.float32).contiguous()
+        B = x.shape[0]
+        y = self.g_a(L.pack_nchw_to_nhwc(x, None, 16))
+        z = self.h_a(y)
+        assert z.shape[-1] == self.eb.channels
+        totals = torch.empty((2 * (len(GROUPS) - 1) + 1, B), device=self.device, dtype=torch.float64)
+        z_hat, _ = L.bottleneck_rate(z, self.eb.channels, self.medians, self.density, bits=totals[-1])
+        hs = self.h_s(z_hat)
+        y_hat = torch.zeros_like(y)
+        passes = []
+
+        def rate_pass(k, i, parity, c0, g, ms):
+            L.elic_rate_pass(ms, 0, g, g, y, c0, parity, y_hat, bits=totals[k])
+            if return_latents:
+                passes.append(dict(slice=i, parity=parity, c0=c0, means=ms[..., :g].permute(0, 3, 1, 2).contiguous(),
+                                   scales=ms[..., g:2 * g].permute(0, 3, 1, 2).contiguous()))
+        self._slice_loop(hs, y_hat, None, rate_pass)
+        xd = self.g_s(y_hat)
+        x_hat = L.scale_clamp(L.nhwc_to_nchw(xd, 3), 1.0, 0.0, (0.0, 1.0))      # .clamp_(0, 1)
+        host = totals.cpu()                                                     # the only device -> host read
+        bits_y = torch.zeros(B, dtype=torch.float64)
+        for k in range(host.shape[0] - 1):
+            bits_y += host[k]
+        out = {"x_hat": x_hat, "bits_y": bits_y, "bits_z": host[-1].clone(), "shape": (int(z.shape[1]), int(z.shape[2]))}
+        if return_latents:
+            out.update(y=y.permute(0, 3, 1, 2).contiguous(), y_hat=y_hat.permute(0, 3, 1, 2).contiguous(),
+                       z=z.permute(0, 3, 1, 2).contiguous(), z_hat=z_hat.permute(0, 3, 1, 2).contiguous(), passes=passes)
+        return out
+
 
 def count_bits(strings):
     """Inference.py:51-67: 8 x total byte length of the nested [y_strings, z_strings] lists."""
@@ -282,3 +341,15 @@ def inference(model, x, patch=64):
     dec = model.decompress(enc["strings"], enc["shape"])
     x_hat = dec["x_hat"][:, :, :h, :w]
     return x_hat, count_bits(enc["strings"])
+
+
+@torch.no_grad()
+def inference_estimate(model, x, patch=64):
+    """``inference`` under the reference's --entropy-estimation: x (3,H,W) in [0,1] -> (x_hat (1,3,H,W), bits as a float), the
+    bits estimated from the likelihoods (``ElicModel.estimate``) instead of counted from coded strings."""
+    x = x.unsqueeze(0)
+    h, w = x.size(2), x.size(3)
+    new_h, new_w = (h + patch - 1) // patch * patch, (w + patch - 1) // patch * patch
+    xp = torch.nn.functional.pad(x, (0, new_w - w, 0, new_h - h))
+    est = model.estimate(xp)
+    return est["x_hat"][:, :, :h, :w], float(est["bits_y"][0] + est["bits_z"][0])

@@ -111,3 +111,86 @@ class EntropyBottleneckCodec:
             sym = self.tables.decode(s, idx).reshape(self.channels, size[0], size[1])
             out[b] = sym.astype(np.float32) + self.medians[:, None, None]
         return out
+
+
+# ---- the factorised density of the hyper-latent (rate estimation: ElicModel.estimate) ----------------------------------------
+EB_FILTERS = (1, 3, 3, 3, 3, 1)         # EntropyBottleneck(filters=(3, 3, 3, 3)): widths of the logits-cumulative chain
+DENSITY_FLOATS = 58                     # per channel: 3+3+3, 3 x (9+3+3), 3+1
+# compressai 1.1.5 (the reference's pin) registers _matrix{i} / _bias{i} / _factor{i}; later releases matrices.{i} / biases.{i} /
+# factors.{i} (ParameterLists).  Neither spelling could be checked against the package: both are accepted.
+_DENSITY_NAMES = (("_matrix{i}", "matrices.{i}"), ("_bias{i}", "biases.{i}"), ("_factor{i}", "factors.{i}"))
+
+
+class DensityParametersMissing(RuntimeError):
+    """The checkpoint holds quantised CDF tables but not the density they were built from: it codes, it cannot estimate."""
+
+
+def density_from_state_dict(sd, prefix="entropy_bottleneck"):
+    """-> ((matrices[5], biases[5], factors[4]) as float64 tensors, []) or (None, [missing keys, first spelling])."""
+    n = len(EB_FILTERS) - 1
+    groups, missing = [], []
+    for (old, new), count in zip(_DENSITY_NAMES, (n, n, n - 1)):
+        got = []
+        for i in range(count):
+            keys = [f"{prefix}.{old.format(i=i)}", f"{prefix}.{new.format(i=i)}"]
+            k = next((k for k in keys if k in sd), None)
+            if k is None:
+                missing.append(keys[0])
+            else:
+                got.append(sd[k].detach().to("cpu", torch.float64))
+        groups.append(got)
+    return (None, missing) if missing else (tuple(groups), [])
+
+
+def pack_density(matrices, biases, factors):
+    """Raw parameters (matrices[i]: (C, out_i, in_i), biases[i]: (C, out_i, 1), factors[i]: (C, out_i, 1)) -> float32 (C, 58):
+    softplus(matrix) / bias / tanh(factor) per layer, taken once in float64 and rounded to fp32 (evc_bottleneck_rate_f32)."""
+    C = matrices[0].shape[0]
+    cols = []
+    for i in range(len(EB_FILTERS) - 1):
+        fo, fi = EB_FILTERS[i + 1], EB_FILTERS[i]
+        assert tuple(matrices[i].shape) == (C, fo, fi) and tuple(biases[i].shape) == (C, fo, 1), (i, matrices[i].shape)
+        cols.append(torch.nn.functional.softplus(matrices[i].double()).reshape(C, fo * fi))
+        cols.append(biases[i].double().reshape(C, fo))
+        if i < len(EB_FILTERS) - 2:
+            assert tuple(factors[i].shape) == (C, fo, 1), (i, factors[i].shape)
+            cols.append(torch.tanh(factors[i].double()).reshape(C, fo))
+    table = torch.cat(cols, 1).float().contiguous()
+    assert table.shape == (C, DENSITY_FLOATS)
+    return table
+
+
+def unpack_density(table):
+    """Inverse of the layout of ``pack_density``: -> (softplus(matrices)[5], biases[5], tanh(factors)[4]), shaped as the raw ones."""
+    C = table.shape[0]
+    mats, bias, fact, o = [], [], [], 0
+    for i in range(len(EB_FILTERS) - 1):
+        fo, fi = EB_FILTERS[i + 1], EB_FILTERS[i]
+        mats.append(table[:, o:o + fo * fi].reshape(C, fo, fi)); o += fo * fi
+        bias.append(table[:, o:o + fo].reshape(C, fo, 1)); o += fo
+        if i < len(EB_FILTERS) - 2:
+            fact.append(table[:, o:o + fo].reshape(C, fo, 1)); o += fo
+    assert o == DENSITY_FLOATS == table.shape[1]
+    return mats, bias, fact
+
+
+def logistic_density_params(scales, medians, dtype=torch.float32):
+    """Raw density parameters for which the factorised density is the logistic ``logistic_bottleneck_tables`` discretises:
+    factors 0 (no tanh term), every matrix entry softplus^-1(a / fan_in) with a = s ** -0.2, so each layer multiplies its
+    (equal) inputs by a and the chain by 1 / s; biases 0 but the last, -median / s: logits(x) = (x - median) / s."""
+    s = torch.as_tensor(np.asarray(scales), dtype=torch.float64)
+    med = torch.as_tensor(np.asarray(medians), dtype=torch.float64)
+    C = s.numel()
+    a = s ** -0.2
+    mats, bias, fact = [], [], []
+    for i in range(len(EB_FILTERS) - 1):
+        fo, fi = EB_FILTERS[i + 1], EB_FILTERS[i]
+        raw = torch.log(torch.expm1(a / fi))                         # softplus(raw) = a / fi
+        mats.append(raw.reshape(C, 1, 1).expand(C, fo, fi).contiguous().to(dtype))
+        b = torch.zeros(C, fo, 1, dtype=torch.float64)
+        if i == len(EB_FILTERS) - 2:
+            b[:, 0, 0] = -med / s
+        bias.append(b.to(dtype))
+        if i < len(EB_FILTERS) - 2:
+            fact.append(torch.zeros(C, fo, 1, dtype=dtype))
+    return mats, bias, fact

@@ -175,6 +175,8 @@ HIP_SYMBOLS = {
                                                                        c_void_p]),
     "evc_elic_scatter_symbols_f32": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     "evc_elic_quantize_f32": (c_int, [c_void_p, c_int, c_int, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p]),
+    "evc_elic_rate_pass_f32": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_void_p]),
+    "evc_bottleneck_rate_f32": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p] * 5),
     "evc_noise_normal_f32": (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_ulonglong, c_uint, c_int, c_void_p]),
     "evc_yuv420_to_rgb": (c_int, [c_void_p] + [c_longlong] * 6 + [c_int] * 5 + [c_void_p, c_int, c_void_p]),
     "evc_rgb_to_yuv420": (c_int, [c_void_p, c_void_p] + [c_longlong] * 6 + [c_int] * 4 + [c_void_p, c_void_p]),
@@ -1126,6 +1128,34 @@ def elic_quantize(y, c0, means, parity):
     _check(hip_lib().evc_elic_quantize_f32(fptr(y), y.shape[-1], c0, fptr(means), C, B, H, 2 * Wh, parity,
                                            fptr(sym, torch.int32), stream_ptr()), "evc_elic_quantize_f32")
     return sym
+
+
+def elic_rate_pass(ms, mean_off, scale_off, C, y, c0, parity, y_hat, bits=None):
+    """One (slice, parity) pass of the rate estimate: ms (B, H, W, ld), y / y_hat (B, H, W, ld_y); fills y_hat at the pass's
+    checkerboard sites of channels c0 .. c0+C and returns bits (B,) float64 on the device (``bits``: where to write them)."""
+    B, H, W, ld = ms.shape
+    assert y.shape == y_hat.shape and y.shape[:3] == ms.shape[:3]
+    if bits is None:
+        bits = torch.empty((B,), device=ms.device, dtype=torch.float64)
+    assert bits.shape == (B,)
+    _check(hip_lib().evc_elic_rate_pass_f32(fptr(ms), ld, mean_off, scale_off, C, fptr(y), y.shape[-1], c0, B, H, W, parity,
+                                            fptr(y_hat), fptr(bits, torch.float64), stream_ptr()), "evc_elic_rate_pass_f32")
+    return bits
+
+
+def bottleneck_rate(z, C, medians, density, bits=None, out=None):
+    """z: (B, H, W, ld) -> (z_hat (B, H, W, ld) with channels < C written, bits (B,) float64 on the device); medians (C,),
+    density (C, 58) as ``entropy.pack_density`` lays it out.  ``out``: the tensor to write z_hat into."""
+    B, H, W, ld = z.shape
+    assert medians.shape == (C,) and density.shape == (C, 58)
+    z_hat = out if out is not None else (torch.zeros_like(z) if ld > C else torch.empty_like(z))
+    assert z_hat.shape == z.shape
+    if bits is None:
+        bits = torch.empty((B,), device=z.device, dtype=torch.float64)
+    assert bits.shape == (B,)
+    _check(hip_lib().evc_bottleneck_rate_f32(fptr(z), ld, C, B, H, W, fptr(medians), fptr(density), fptr(z_hat),
+                                             fptr(bits, torch.float64), stream_ptr()), "evc_bottleneck_rate_f32")
+    return z_hat, bits
 
 
 # ---- host rANS -------------------------------------------------------------------------------

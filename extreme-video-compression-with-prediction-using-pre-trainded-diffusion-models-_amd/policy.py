@@ -128,6 +128,18 @@ def coded_batch(model, x, patch):
     return dec, [count_bits(s) for s in strings], strings, enc["shape"]
 
 
+def estimated_batch(model, x, patch):
+    """``coded_batch`` under --entropy-estimation: -> (x_hat, bits[n] as Python floats, None, shape).  The frames are those of
+    ``coded_batch`` bit for bit; the bits are the sums of -log2(likelihood) of ``ElicModel.estimate`` (no strings exist, hence
+    None), read back once per call."""
+    h, w = x.shape[-2:]
+    ph, pw = (-h) % patch, (-w) % patch
+    xp = torch.nn.functional.pad(x, (0, pw, 0, ph))
+    est = model.estimate(xp)
+    bits = (est["bits_y"] + est["bits_z"]).tolist()
+    return est["x_hat"][:, :, :h, :w], bits, None, est["shape"]
+
+
 class _Job:
     __slots__ = ("uid", "sid", "vid", "q", "thr", "x", "ids", "d", "bits", "round", "segments", "strings")
 
@@ -182,7 +194,7 @@ class StateGrouper:
 
 def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=30, max_batch=32, seed=0,
                bpp_limit=1.0, device="cuda", log=None, noise_source=None, stats=None, noise="torch", batch_invariant=False,
-               noise_streams="job", share=False):
+               noise_streams="job", share=False, estimate=False):
     """The reference's sweep, batched.
 
     decoder:       ClipDecoder (only ``generate`` is used: the generator does not depend on q)
@@ -215,6 +227,9 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
                    frames merge again.  With ``batch_invariant`` every job's frames are bitwise what share=False gives under
                    the same streams; in the default mode they differ in the last bits, as frames of launches of other
                    shapes do
+    estimate:      key frames go through ``estimated_batch`` instead of ``coded_batch`` (--entropy-estimation): the same frames,
+                   ``bits`` are float estimates and there are no strings (``key_strings`` holds None: such results cannot be
+                   packed into job streams)
     stats:         optional dict, filled with the launch-size histogram {samples (= states) in a launch: generation launches},
                    the number of generation rounds and of key frames coded, the host seconds spent drawing noise, and per
                    round the number of states generated (``states``) and of active jobs they served (``jobs_served``)
@@ -263,10 +278,10 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
             for c0 in range(0, len(todo), max_batch):
                 part = todo[c0:c0 + max_batch]
                 x = torch.stack([gt_dev[v][f] for (v, _, f) in part], 0)
-                xh, bits, strings, shape = coded_batch(models[q], x, patch)
+                xh, bits, strings, shape = (estimated_batch if estimate else coded_batch)(models[q], x, patch)
                 shapes.append(tuple(shape))
                 for i, k in enumerate(part):
-                    key_cache[k] = (xh[i], bits[i], strings[i])
+                    key_cache[k] = (xh[i], bits[i], None if strings is None else strings[i])
 
     def add_keys(job, fs):
         for f in fs:

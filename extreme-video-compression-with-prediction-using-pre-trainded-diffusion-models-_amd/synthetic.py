@@ -200,6 +200,23 @@ def elic_param_shapes(N=192, M=320):
 def elic_state_dict(seed, N=192, M=320, gain=1.0):
     """Random ELIC checkpoint in the reference layout.  ParamAggregation scale outputs get a positive bias so
     the coded symbols are mostly in-table (the bypass path still occurs, but is not the only one exercised)."""
+    return _elic_state_dict(seed, N, M, gain)[0]
+
+
+def elic_state_dict_with_density(seed, N=192, M=320, gain=1.0, naming="compressai-1.1.5"):
+    """``elic_state_dict(seed)`` (the same draws, the same tensors) plus the parameters of the entropy bottleneck's density,
+    chosen so that the density IS the logistic its tables were built from (entropy.logistic_density_params): the rate
+    ``ElicModel.estimate`` reports for z is then the ideal code length under the very tables ``compress`` codes with.
+    ``naming``: "compressai-1.1.5" (_matrix{i} / _bias{i} / _factor{i}) or "later" (matrices.{i} / biases.{i} / factors.{i})."""
+    sd, eb_scales, med = _elic_state_dict(seed, N, M, gain)
+    names = {"compressai-1.1.5": ("_matrix{i}", "_bias{i}", "_factor{i}"), "later": ("matrices.{i}", "biases.{i}", "factors.{i}")}[naming]
+    for name, tensors in zip(names, entropy.logistic_density_params(eb_scales, med)):
+        for i, t in enumerate(tensors):
+            sd["entropy_bottleneck." + name.format(i=i)] = t
+    return sd
+
+
+def _elic_state_dict(seed, N, M, gain):
     rng = np.random.default_rng(seed)
     G = [0, 16, 16, 32, 64, 192]
     sd = {}
@@ -234,7 +251,7 @@ def elic_state_dict(seed, N=192, M=320, gain=1.0):
     sd["entropy_bottleneck._quantized_cdf"] = torch.from_numpy(eb.cdf.copy())
     sd["entropy_bottleneck._cdf_length"] = torch.from_numpy(eb.length.copy())
     sd["entropy_bottleneck._offset"] = torch.from_numpy(eb.offset.copy())
-    return sd
+    return sd, eb_scales, med
 
 
 # ---- clips ------------------------------------------------------------------------------------------

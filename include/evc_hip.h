@@ -387,6 +387,30 @@ int evc_elic_scatter_symbols_f32(const int* symbols, const float* means, float* 
 int evc_elic_quantize_f32(const float* y, int ld, int c0, const float* means, int C, int B, int H, int W,
                           int parity, int* symbols, void* stream);
 
+/* ---- ELIC rate estimation (csrc/rate.hip): TestModel.inference (Network.py:534-640), the rate without an entropy coder --------
+ * Both kernels run one workgroup per sample and add -log2(likelihood) over the sample's sites in an order that depends on
+ * (C, H, W) only (per-lane strided partial sums in double, wave shuffle tree, fixed pass over the wave totals; a plain store, no
+ * atomics): bits[b] is the same pattern whatever else is in the batch.  compressai's bounds are torch.max(x, bound): a NaN in
+ * y, a mean, a scale or z gives NaN bits for that sample (and torch's NaN in y_hat / z_hat), +-inf in y - mean the floor value
+ * -log2(1e-9); other samples are unaffected.  Caller's stream, no allocation.
+ *
+ * One (slice, parity) pass of the Gaussian-conditional model.  Replaces evc_elic_gather_params_f32 + evc_elic_quantize_f32 +
+ * evc_elic_scatter_symbols_f32 + the host range coder of that pass: GaussianConditional.forward in eval mode (compressai 1.1.5:
+ * quantize "dequantize", _likelihood with its fp32 erfc difference, scale bound 0.11 and likelihood bound 1e-9).  At the
+ * checkerboard sites of `parity` (same sites as above) of ms [B][H][W][ld] = [.. means at mean_off .. scales at scale_off ..] and
+ * y [B][H][W][ld_y] at channels c0 .. c0+C: y_hat[b][h][w][c0 + c] = rint(y - mean) + mean (bit-identical to
+ * evc_elic_scatter_symbols_f32 of the coded path; all other elements untouched), bits[b] = sum of -log2 p. */
+int evc_elic_rate_pass_f32(const float* ms, int ld, int mean_off, int scale_off, int C, const float* y, int ld_y, int c0,
+                           int B, int H, int W, int parity, float* y_hat, double* bits, void* stream);
+/* The factorised density of the hyper-latent.  Replaces EntropyBottleneck.compress / decompress on the host (entropy.py
+ * EntropyBottleneckCodec + the range coder): EntropyBottleneck.forward in eval mode (compressai 1.1.5, filters (3,3,3,3)).
+ * z, z_hat [B][H][W][ld] (C <= ld channels used), medians [C], density [C][58]: per channel softplus(matrix), bias, tanh(factor)
+ * of the five layers packed 3+3+3, 3 x (9+3+3), 3+1 (matrices row-major [out][in]; entropy.pack_density).
+ * z_hat = rint(z - median) + median, bits[b] = sum of -log2 max(|sigmoid(s*upper) - sigmoid(s*lower)|, 1e-9) with lower / upper =
+ * logits_cumulative(z_hat -+ 0.5), s = -sign(lower + upper). */
+int evc_bottleneck_rate_f32(const float* z, int ld, int C, int B, int H, int W, const float* medians, const float* density,
+                            float* z_hat, double* bits, void* stream);
+
 /* ---- ELIC stride-2 convolutions, polyphase form (csrc/stride2.hip) ----------------------------------------------
  * compressai deconv() = ConvTranspose2d(k 5, stride 2, padding 2, output_padding 1) and conv() = Conv2d(k 5, stride 2,
  * padding 2) (reference Network.py:88-138).  Exactly the same sums as the direct forms, as ONE 3x3 stride-1 convolution
