@@ -14,9 +14,11 @@
 // One wave = 32 queries; a workgroup of WAVES waves shares each 32-key K/V tile through LDS.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <type_traits>
 #include "../../include/evc_hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef EVC_ATTN_WG_TARGET
 #define EVC_ATTN_WG_TARGET 512      // workgroups a key-split launch should offer (2 per CU)
@@ -588,6 +590,420 @@ __global__ void attention_merge_kernel(const float* __restrict__ part_o, const f
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Short sequences (N <= 256 keys: the 16x16 and 8x8 levels), default mode.  There are only B * heads * N / 32 query blocks
+// of one wave (72 and 216 at B = 9), so the kernels above either run one wave per workgroup down a serial chain of MFMAs
+// (8x8) or cut the keys into parts across workgroups and pay for a partial-O round trip through memory plus a merge launch
+// (16x16).  Here a workgroup is still one (sample, head, 32-query block) but has 4 waves that share the work of every key
+// tile, so the keys are never split and nothing is merged:
+//   S^T = K Q^T   the reduction over D is cut into 4 slices, one per wave; the 4 partial tiles meet in LDS and every wave
+//                 sums them in the same fixed order, so all 4 hold the same S^T bit for bit
+//   softmax       lane-local as above, repeated in every wave on identical numbers (16 exps per lane and tile)
+//   O^T = V^T P^T the D / 32 output tiles are dealt to the waves (tile t -> wave t % 4); P comes from the wave's own registers
+// K and V are staged by all 256 threads.  Cutting the KEY tiles over the waves instead would need 4 distinct tiles resident
+// (4 x 55 KB of fp16 planes at D = 192 against 160 KB of LDS) and an in-workgroup merge of 4 partial O; with the D cut
+// every wave sees every key and the softmax state needs no merge at all.
+constexpr int ATTN_SX_FLOATS = 4 * 16 * 64;      // the exchange image: one partial S^T tile per wave (16 KB)
+
+// the wave's partial S^T tile -> LDS; returns the sum of the 4 waves' partials ((w0 + w1) + w2) + w3.  Contains a barrier.
+__device__ __forceinline__ f32x16 attention_sum_partials(float* sx, int wave, int lane, const f32x16& s) {
+    float4* const img = reinterpret_cast<float4*>(sx);               // [wave][g][lane] float4
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+        img[(wave * 4 + g) * 64 + lane] = make_float4(s[4 * g], s[4 * g + 1], s[4 * g + 2], s[4 * g + 3]);
+    __syncthreads();
+    f32x16 t;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const float4 a = img[(0 * 4 + g) * 64 + lane], b = img[(1 * 4 + g) * 64 + lane];
+        const float4 c = img[(2 * 4 + g) * 64 + lane], d = img[(3 * 4 + g) * 64 + lane];
+        t[4 * g] = ((a.x + b.x) + c.x) + d.x;
+        t[4 * g + 1] = ((a.y + b.y) + c.y) + d.y;
+        t[4 * g + 2] = ((a.z + b.z) + c.z) + d.z;
+        t[4 * g + 3] = ((a.w + b.w) + c.w) + d.w;
+    }
+    return t;
+}
+
+// exact-f32 form.  A workgroup walks all the key tiles alone on its CU, so a tile's trip to memory must not be waited for: TWO
+// register sets and TWO LDS images -- the loads of tile t + 1 are issued before tile t is written to LDS and computed (8x8:
+// both tiles are in flight at once), and a wave that is done with tile t stores tile t + 1 into the other image without
+// waiting for the rest.  Two barriers per tile (image ready, exchange).
+// LDS: one exchange image | 2 x ([32][LDK] K, [32][LDK] V).
+template <int D>
+__global__ __launch_bounds__(256, 1) void attention_short_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                 const float* __restrict__ v, int ld,
+                                                                 float* __restrict__ out, int ld_out, int N, float scale) {
+    constexpr int LDK = D + 4;
+    constexpr int NGW = D / 32;              // 8-deep k groups of the QK^T product per wave (D / 8 in all)
+    constexpr int DT = D / 32;               // 32-wide d tiles of the PV product ...
+    constexpr int DTW = (DT + 3) / 4;        // ... per wave at most
+    constexpr int TILE = 2 * 32 * LDK;       // floats per staged tile (K | V)
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* const sx = smem;
+    float* const kv = smem + ATTN_SX_FLOATS;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l31 = lane & 31, half = lane >> 5;
+    const int b = blockIdx.z, h = blockIdx.y;
+    const size_t base = (size_t)b * N * ld + (size_t)h * D;
+    const int myq = blockIdx.x * 32 + l31;
+    const bool qvalid = myq < N;
+    const int d0 = 8 * NGW * wave;           // this wave's slice of the reduction over D
+
+    float4 qf[NGW];
+    {
+        const float* qp = q + base + (size_t)(qvalid ? myq : 0) * ld + d0 + 4 * half;
+#pragma unroll
+        for (int g = 0; g < NGW; ++g)
+            qf[g] = qvalid ? *reinterpret_cast<const float4*>(qp + 8 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+
+    f32x16 o[DTW];
+#pragma unroll
+    for (int i = 0; i < DTW; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;
+
+    // staging: DT float4 of K and of V per thread and tile, issued unconditionally from a clamped (valid) row and masked when
+    // stored, so that the number of loads in flight is known at compile time
+    struct Staged { f32x4 k[DT], v[DT]; } ra, rb;
+    const float* const kb = k + base;
+    const float* const vb = v + base;
+    auto load_tile = [&](Staged& r, int k0) {
+#pragma unroll
+        for (int i = 0; i < DT; ++i) {
+            const int u = tid + 256 * i;
+            const int row = u / (D / 4), c4 = u - row * (D / 4);
+            const unsigned at = (unsigned)(min(k0 + row, N - 1) * ld + 4 * c4);          // uniform base + 32-bit offset
+            r.k[i] = *reinterpret_cast<const f32x4*>(kb + at);
+            r.v[i] = *reinterpret_cast<const f32x4*>(vb + at);
+        }
+    };
+    auto store_tile = [&](const Staged& r, int k0, float* Ks) {
+#pragma unroll
+        for (int i = 0; i < DT; ++i) {
+            const int u = tid + 256 * i;
+            const int row = u / (D / 4), c4 = u - row * (D / 4);
+            const bool ok = k0 + row < N;
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            *reinterpret_cast<f32x4*>(Ks + row * LDK + 4 * c4) = ok ? r.k[i] : z;
+            *reinterpret_cast<f32x4*>(Ks + (32 + row) * LDK + 4 * c4) = ok ? r.v[i] : z;
+        }
+    };
+
+    auto tile = [&](int k0, const float* Ks) {
+        const float* const Vs = Ks + 32 * LDK;
+
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+        const float* kp = Ks + l31 * LDK + d0 + 4 * half;
+#pragma unroll
+        for (int g = 0; g < NGW; ++g) {
+            const float4 a = *reinterpret_cast<const float4*>(kp + 8 * g);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, qf[g].x, s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, qf[g].y, s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, qf[g].z, s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, qf[g].w, s, 0, 0, 0);
+        }
+        s = attention_sum_partials(sx, wave, lane, s);
+
+        // online softmax, as in attention_kernel
+        float m_tile = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            s[r] = key < N ? s[r] * scale : -INFINITY;
+            m_tile = fmaxf(m_tile, s[r]);
+        }
+        m_tile = fmaxf(m_tile, __shfl_xor(m_tile, 32));
+        const float m_new = fmaxf(m_run, m_tile);
+        const float alpha = __expf(m_run - m_new);
+        float psum = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            s[r] = __expf(s[r] - m_new);
+            psum += s[r];
+        }
+        l_run = l_run * alpha + psum;
+        m_run = m_new;
+#pragma unroll
+        for (int i = 0; i < DTW; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
+
+#pragma unroll
+        for (int i = 0; i < DTW; ++i) {
+            const int t = wave + 4 * i;
+            if (t < DT) {                                     // wave-uniform
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int kr = (r & 3) + 8 * (r >> 2) + 4 * half;
+                    o[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[kr * LDK + l31 + 32 * t], s[r], o[i], 0, 0, 0);
+                }
+            }
+        }
+    };
+
+    load_tile(ra, 0);
+    // two tiles per trip: the register sets alternate.  The loads of the next tile are issued whether or not there is one (its
+    // rows clamp to the last key): a branch around them would leave the number of loads in flight unknown to the compiler,
+    // which then waits for all of them before the older set is used.
+    for (int k0 = 0; k0 < N; k0 += 64) {
+        load_tile(rb, k0 + 32);
+        store_tile(ra, k0, kv);
+        __syncthreads();
+        tile(k0, kv);
+        if (k0 + 32 >= N) break;
+        load_tile(ra, k0 + 64);
+        store_tile(rb, k0 + 32, kv + TILE);
+        __syncthreads();
+        tile(k0 + 32, kv + TILE);
+    }
+
+    const float inv = 1.0f / (l_run + __shfl_xor(l_run, 32));
+    if (qvalid) {
+        float* op = out + ((size_t)b * N + myq) * ld_out + (size_t)h * D;
+#pragma unroll
+        for (int i = 0; i < DTW; ++i) {
+            const int t = wave + 4 * i;
+            if (t < DT) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<float4*>(op + 32 * t + 8 * g + 4 * half) =
+                        make_float4(o[i][4 * g] * inv, o[i][4 * g + 1] * inv, o[i][4 * g + 2] * inv, o[i][4 * g + 3] * inv);
+            }
+        }
+    }
+}
+
+// fp16-split form: operands, conversion, lazy softmax reference and LDS tile image exactly as attention_f16_kernel<D, 4>;
+// k-step st of the QK^T product belongs to wave st % 4.  A workgroup walks all the key tiles (up to 8) alone on its CU, so a
+// tile's trip to memory must not be waited for: TWO register sets and TWO LDS images -- the loads of tile t + 1 are issued
+// before tile t is converted (scale, split, transpose -> LDS) and computed, and a wave that is done with tile t converts tile
+// t + 1 into the other image without waiting for the rest.  Two barriers per tile (image ready, exchange).
+// LDS: one exchange image | 2 x ([2 planes][32 keys][KROW] K | [2 planes][D][VROW] V^T).
+template <int D>
+__global__ __launch_bounds__(256, 1) void attention_short_f16_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                     const float* __restrict__ v, int ld,
+                                                                     float* __restrict__ out, int ld_out, int N, float scale,
+                                                                     const unsigned* __restrict__ bounds) {
+    constexpr int NKS = D / 16;              // k-steps of the QK^T product ...
+    constexpr int NKSW = (NKS + 3) / 4;      // ... per wave at most
+    constexpr int DT = D / 32;
+    constexpr int DTW = (DT + 3) / 4;
+    constexpr int NT = 256;
+    constexpr int KROW = 2 * D + 16;
+    constexpr int VROW = 64 + 16;
+    constexpr int KPL = 32 * KROW, VPL = D * VROW;
+    extern __shared__ __attribute__((aligned(16))) char smem_h[];
+    float* const sx = reinterpret_cast<float*>(smem_h);
+    constexpr int TILE_BYTES = 2 * KPL + 2 * VPL;
+    char* const img0 = smem_h + ATTN_SX_FLOATS * sizeof(float);
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l31 = lane & 31, half = lane >> 5;
+    const int b = blockIdx.z, h = blockIdx.y;
+    const size_t base = (size_t)b * N * ld + (size_t)h * D;
+    const int myq = blockIdx.x * 32 + l31;
+    const bool qvalid = myq < N;
+
+    const float sq = pow2_scale_for(__uint_as_float(bounds[0]), 9);
+    const float sk = pow2_scale_for(__uint_as_float(bounds[1]), 9);
+    const float sv = pow2_scale_for(__uint_as_float(bounds[2]), 9);
+    constexpr float SP = 1024.0f;
+    const float s_mul = scale / (sq * sk);
+    const float o_mul = 1.0f / (SP * sv);
+
+    h16x8 q1[NKSW], q2[NKSW];
+    {
+        const float* qp = q + base + (size_t)(qvalid ? myq : 0) * ld + 8 * half;
+#pragma unroll
+        for (int i = 0; i < NKSW; ++i) {
+            const int st = wave + 4 * i;
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f), c = a;
+            if (qvalid && st < NKS) {
+                a = *reinterpret_cast<const float4*>(qp + 16 * st);
+                c = *reinterpret_cast<const float4*>(qp + 16 * st + 4);
+            }
+            const float x[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { _Float16 u, w; split2h(x[j] * sq, u, w); q1[i][j] = u; q2[i][j] = w; }
+        }
+    }
+
+    f32x16 o[DTW];
+#pragma unroll
+    for (int i = 0; i < DTW; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
+    float m_run = -INFINITY, l_run = 0.f;
+
+    const int k_rd = l31 * KROW + 16 * half;
+    const int v_rd = l31 * VROW + 16 * half;
+
+    constexpr int KU = (32 * (D / 8) + NT - 1) / NT;
+    constexpr int VU = 8 * D / NT;
+    struct Staged { float4 kreg[KU][2]; float vreg[VU][4]; } ra, rb;
+    // every load is issued unconditionally from a clamped (valid) address and masked when it is stored: the number of loads in
+    // flight is then known at compile time, so waiting for one register set does not wait for the other
+    const float* const kb = k + base;
+    const float* const vb = v + base;
+    auto load_tile = [&](Staged& r, int k0) {
+#pragma unroll
+        for (int i = 0; i < KU; ++i) {
+            const int u = tid + NT * i;
+            const int row = u / (D / 8), ch = u - row * (D / 8);
+            const float* kp = kb + (unsigned)(min(k0 + row, N - 1) * ld + 8 * ch);      // uniform base + 32-bit offset
+            r.kreg[i][0] = *reinterpret_cast<const float4*>(kp);
+            r.kreg[i][1] = *reinterpret_cast<const float4*>(kp + 4);
+        }
+#pragma unroll
+        for (int i = 0; i < VU; ++i) {
+            const int u = tid + NT * i;
+            const int g = u / D, d = u - g * D;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r.vreg[i][e] = vb[(unsigned)(min(k0 + 4 * g + e, N - 1) * ld + d)];
+        }
+    };
+    auto store_tile = [&](const Staged& r, int k0, char* Ks, auto ragged) {      // ragged: the tile has rows past the last key
+        auto& kreg = r.kreg;
+        auto& vreg = r.vreg;
+        char* const Vs = Ks + 2 * KPL;
+#pragma unroll
+        for (int i = 0; i < KU; ++i) {
+            const int u = tid + NT * i;
+            if ((32 * (D / 8)) % NT != 0 && u >= 32 * (D / 8)) break;       // D = 32 only
+            const int row = u / (D / 8), ch = u - row * (D / 8);
+            const float x[8] = {kreg[i][0].x, kreg[i][0].y, kreg[i][0].z, kreg[i][0].w,
+                                kreg[i][1].x, kreg[i][1].y, kreg[i][1].z, kreg[i][1].w};
+            h16x8 p1, p2;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { _Float16 uu, ww; split2h(!ragged() || k0 + row < N ? x[j] * sk : 0.f, uu, ww); p1[j] = uu; p2[j] = ww; }
+            char* dst = Ks + row * KROW + 16 * ch;
+            *reinterpret_cast<h16x8*>(dst) = p1;
+            *reinterpret_cast<h16x8*>(dst + KPL) = p2;
+        }
+#pragma unroll
+        for (int i = 0; i < VU; ++i) {
+            const int u = tid + NT * i;
+            const int g = u / D, d = u - g * D;                             // (8 * D units: a multiple of the 256 threads)
+            h16x4 p1, p2;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { _Float16 uu, ww; split2h(!ragged() || k0 + 4 * g + e < N ? vreg[i][e] * sv : 0.f, uu, ww); p1[e] = uu; p2[e] = ww; }
+            // keys 4g .. 4g+3 sit at positions 16*(g>>2) + 8*(g&1) + 4*((g>>1)&1) + (0..3)
+            const int pos = 16 * (g >> 2) + 8 * (g & 1) + 4 * ((g >> 1) & 1);
+            char* dst = Vs + d * VROW + 2 * pos;
+            *reinterpret_cast<h16x4*>(dst) = p1;
+            *reinterpret_cast<h16x4*>(dst + VPL) = p2;
+        }
+    };
+
+    auto tile = [&](int k0, const char* Ks) {
+        const char* const Vs = Ks + 2 * KPL;
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+        for (int i = 0; i < NKSW; ++i) {
+            const int st = wave + 4 * i;
+            if (st < NKS) {                                       // wave-uniform
+                const h16x8 k1 = *reinterpret_cast<const h16x8*>(Ks + k_rd + 32 * st);
+                const h16x8 k2 = *reinterpret_cast<const h16x8*>(Ks + KPL + k_rd + 32 * st);
+                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(k2, q1[i], s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(k1, q2[i], s, 0, 0, 0);
+                s = __builtin_amdgcn_mfma_f32_32x32x16_f16(k1, q1[i], s, 0, 0, 0);
+            }
+        }
+        s = attention_sum_partials(sx, wave, lane, s);
+
+        // lazy-reference online softmax, as in attention_f16_kernel
+        constexpr float LAZY_TAU = 3.5f;
+        float m_tile = -INFINITY;
+        if (k0 + 32 > N) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                s[r] = key < N ? s[r] * s_mul : -INFINITY;
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[r] *= s_mul;
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) m_tile = fmaxf(m_tile, s[r]);
+        m_tile = fmaxf(m_tile, __shfl_xor(m_tile, 32));
+        const float m_new = m_tile > m_run + LAZY_TAU ? m_tile : m_run;
+        const float alpha = __expf(m_run - m_new);
+        float psum = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            s[r] = __expf(s[r] - m_new);
+            psum += s[r];
+        }
+        l_run = l_run * alpha + psum;
+        m_run = m_new;
+        if (__any(alpha != 1.0f)) {
+#pragma unroll
+            for (int i = 0; i < DTW; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
+        }
+
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            h16x8 p1, p2;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { _Float16 uu, ww; split2h(s[8 * s2 + j] * SP, uu, ww); p1[j] = uu; p2[j] = ww; }
+#pragma unroll
+            for (int i = 0; i < DTW; ++i) {
+                const int t = wave + 4 * i;
+                if (t < DT) {                                     // wave-uniform
+                    const h16x8 v1 = *reinterpret_cast<const h16x8*>(Vs + v_rd + 32 * t * VROW + 32 * s2);
+                    const h16x8 v2 = *reinterpret_cast<const h16x8*>(Vs + VPL + v_rd + 32 * t * VROW + 32 * s2);
+                    o[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v2, p1, o[i], 0, 0, 0);
+                    o[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1, p2, o[i], 0, 0, 0);
+                    o[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1, p1, o[i], 0, 0, 0);
+                }
+            }
+        }
+    };
+
+    load_tile(ra, 0);
+    // two tiles per trip: the register sets alternate.  The loads of the next tile are issued whether or not there is one (its
+    // rows clamp to the last key): a branch around them would leave the number of loads in flight unknown to the compiler,
+    // which then waits for all of them before the older set is used.
+    for (int k0 = 0; k0 < N; k0 += 64) {
+        load_tile(rb, k0 + 32);
+        if (k0 + 32 > N) store_tile(ra, k0, img0, std::true_type()); else store_tile(ra, k0, img0, std::false_type());
+        __syncthreads();
+        tile(k0, img0);
+        if (k0 + 32 >= N) break;
+        load_tile(ra, k0 + 64);
+        if (k0 + 64 > N) store_tile(rb, k0 + 32, img0 + TILE_BYTES, std::true_type());
+        else store_tile(rb, k0 + 32, img0 + TILE_BYTES, std::false_type());
+        __syncthreads();
+        tile(k0 + 32, img0 + TILE_BYTES);
+    }
+
+    const float inv = o_mul / (l_run + __shfl_xor(l_run, 32));
+    if (qvalid) {
+        float* op = out + ((size_t)b * N + myq) * ld_out + (size_t)h * D;
+#pragma unroll
+        for (int i = 0; i < DTW; ++i) {
+            const int t = wave + 4 * i;
+            if (t < DT) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<float4*>(op + 32 * t + 8 * g + 4 * half) =
+                        make_float4(o[i][4 * g] * inv, o[i][4 * g + 1] * inv, o[i][4 * g + 2] * inv, o[i][4 * g + 3] * inv);
+            }
+        }
+    }
+}
+
 struct AttnPlan { int waves, kparts, tiles_per_part; };
 
 // Waves per workgroup as before; then, when the launch would leave SIMDs idle (fewer than ~1024 waves) and the key
@@ -646,6 +1062,7 @@ AttnPlan attention_plan_f16(int B, int heads, int N) {
 
 int g_attn_pre = 1;       // run-time switch (evc_attention_set_option "kv_planes"): K / V converted once per launch (A/B)
 int g_attn_f16_min_keys = 128;   // run-time switch "f16_min_keys": fewest keys for which the fp16-split kernel is used
+int g_attn_short = 1;     // run-time switch "short_seq": N <= 256 keys on the one-launch short-sequence kernels (default mode only)
 
 // bytes of the key-part buffers at the head of the workspace (part_o | part_ml), rounded to 16
 // (`inv`: batch-invariant mode plans at the reference batch EVC_INVARIANT_REF_BATCH of include/evc_hip.h, whatever B is:
@@ -679,6 +1096,41 @@ int launch_f32(dim3 grid, size_t lds, hipStream_t st, const float* q, const floa
     return EVC_OK;
 }
 
+// dynamic LDS above the 64 KB a kernel gets without asking: raise the kernel's limit once per device (`done`: one bit per id)
+int attention_allow_lds(const void* fn, size_t lds, unsigned long long& done) {
+    if (lds <= 64 * 1024) return EVC_OK;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return EVC_ELAUNCH;
+    const unsigned long long bit = 1ULL << (dev & 63);
+    if (!(__atomic_load_n(&done, __ATOMIC_ACQUIRE) & bit)) {
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return EVC_ELAUNCH;
+        __atomic_fetch_or(&done, bit, __ATOMIC_RELEASE);
+    }
+    return EVC_OK;
+}
+
+// N <= 256 keys, D <= 192: one launch of 4-wave workgroups, one per (sample, head, 32-query block); no workspace
+template <int D>
+int launch_short(const float* q, const float* k, const float* v, int ld, float* out, int ld_out, int B, int heads, int N,
+                 float scale, const unsigned* bounds, bool f16, hipStream_t st) {
+    constexpr size_t SX = ATTN_SX_FLOATS * sizeof(float);
+    const dim3 grid((N + 31) / 32, heads, B);
+    if (f16) {
+        const size_t lds = SX + 2 * (size_t)attention_tile_bytes<D>();
+        static unsigned long long done = 0;
+        const int rc = attention_allow_lds(reinterpret_cast<const void*>(&attention_short_f16_kernel<D>), lds, done);
+        if (rc != EVC_OK) return rc;
+        hipLaunchKernelGGL((attention_short_f16_kernel<D>), grid, dim3(256), lds, st, q, k, v, ld, out, ld_out, N, scale, bounds);
+    } else {
+        const size_t lds = SX + 2 * (size_t)2 * 32 * (D + 4) * sizeof(float);
+        static unsigned long long done = 0;
+        const int rc = attention_allow_lds(reinterpret_cast<const void*>(&attention_short_kernel<D>), lds, done);
+        if (rc != EVC_OK) return rc;
+        hipLaunchKernelGGL((attention_short_kernel<D>), grid, dim3(256), lds, st, q, k, v, ld, out, ld_out, N, scale);
+    }
+    return hipGetLastError() == hipSuccess ? EVC_OK : EVC_ELAUNCH;
+}
+
 template <int D>
 int launch(const float* q, const float* k, const float* v, int ld, float* out, int ld_out, int B, int heads, int N,
            float scale, float* ws, const unsigned* bounds, hipStream_t st, bool inv) {
@@ -693,6 +1145,8 @@ int launch(const float* q, const float* k, const float* v, int ld, float* out, i
     // head widths above 192 stay on the f32 kernel: the fp16 kernel keeps Q (both planes) and O in registers, D/2 + D/2 of them
     constexpr bool F16_OK = D <= 192;
     const bool use_f16 = F16_OK && bounds && N >= min_keys;
+    if constexpr (F16_OK)
+        if (!inv && g_attn_short && N <= 256) return launch_short<D>(q, k, v, ld, out, ld_out, B, heads, N, scale, bounds, use_f16, st);
     const AttnPlan pl = (use_f16 && have_ws) ? attention_plan_f16(Bp, heads, N) : attention_plan(Bp, heads, N, have_ws);
     const int waves = pl.waves;
     if (!ws && (pl.kparts > 1 || (use_f16 && pre && waves == 4 && N >= 512 && inv))) return EVC_EINVAL;   // the plan needs a workspace
@@ -807,6 +1261,7 @@ extern "C" int evc_attention_set_option(const char* name, int value) {
     const auto is = [&](const char* s) { int i = 0; while (s[i] && s[i] == name[i]) ++i; return s[i] == 0 && name[i] == 0; };
     if (is("kv_planes")) { g_attn_pre = value; return EVC_OK; }
     if (is("f16_min_keys")) { g_attn_f16_min_keys = value; return EVC_OK; }
+    if (is("short_seq")) { g_attn_short = value; return EVC_OK; }
     return EVC_EINVAL;
 }
 

@@ -822,7 +822,7 @@ def conv_workspace_bytes(B, H, W, Ci, Co, KH, KW, splits=0, arith=None):
 
 
 def attention_set_option(name, value):
-    """A/B switch of the attention kernels (include/evc_hip.h: "kv_planes")."""
+    """A/B switch of the attention kernels (include/evc_hip.h: "kv_planes", "f16_min_keys", "short_seq")."""
     if hip_lib().evc_attention_set_option(name.encode(), int(value)) != 0:
         raise EvcKernelError(f"unknown attention option {name!r}")
 

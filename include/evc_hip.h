@@ -310,6 +310,11 @@ long long evc_attention_workspace_bytes(int B, int heads, int N, int D);
  * images of its LDS layout (a pre-pass into the workspace) and stages them by LDS-DMA, instead of converting every 32-key tile
  * again in every query block.  Same numbers either way.  "f16_min_keys" (default 128): fewest keys for which
  * evc_attention_f16x3_f32 runs the fp16-split kernel (below it the f32-MFMA kernel: B = 9, 64 keys, 4 heads of 192: 26 us vs 40 us).
+ * "short_seq" (default 1): N <= 256 keys and D <= 192 run the short-sequence kernels -- ONE launch of 4-wave workgroups, one per
+ * (sample, head, 32-query block), whose waves cut the reduction over D of K Q^T and deal out the D / 32 tiles of P V; no key
+ * parts, no merge launch, the workspace is not used (evc_attention_workspace_bytes is unchanged).  The arithmetic is chosen as
+ * before (f32 MFMA, or the fp16 split from "f16_min_keys" keys on).  0: the kernels and plans used above 256 keys.  B = 9, 4 heads
+ * of 192, 64 keys: 26 -> 11 us; 3 heads, 256 keys: 29 -> 27 us.  evc_attention_invariant_f32 ignores all three.
  * Returns EVC_EINVAL for an unknown name. */
 int evc_attention_set_option(const char* name, int value);
 int evc_attention_ws_f32(const float* q, const float* k, const float* v, int ld_qkv, float* out, int ld_out, int B,
