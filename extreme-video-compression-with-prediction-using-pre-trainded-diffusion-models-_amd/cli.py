@@ -20,6 +20,8 @@ reference's benchmark conventions, converted by the HIP kernels of csrc/yuv.hip)
 as ``.y4m`` and ``--yuv-metrics`` adds the PSNR of the reference's codec benchmark.
 ``--entropy-estimation`` (a reference flag) reports every key frame's rate as the sum of -log2(likelihood), computed on the GPU
 (``ElicModel.estimate``) instead of the length of range-coded strings: same frames, fractional bits.
+``--ssim`` adds the reference's SSIM (fvd_utils/calculate_ssim.py; ssim.py, csrc/ssim.hip) of every job:
+one more printed line and ``ssim_<idx>.npy`` / ``ssim_frames_<idx>.npy``; a reported value, never a decision rule.
 """
 import argparse
 import os
@@ -122,10 +124,16 @@ def build_parser():
                    help="also save psnr_yuv_frames_<idx>.npy and psnr_yuv_<idx>.npy: the PSNR of the reference's codec benchmark "
                         "(bench_uvg.py:487,508-509) -- original and decoded clip both go RGB -> 8-bit 4:2:0 -> RGB (bicubic) -> "
                         "rounded to 8 bits")
+    p.add_argument("--ssim", action="store_true",
+                   help="also report each job's SSIM against the original clip (fvd_utils/calculate_ssim.py: 11x11 Gaussian window, "
+                        "float64, mean over the valid region and the 3 channels) and save ssim_frames_<idx>.npy (jobs, 30) and "
+                        "ssim_<idx>.npy; with --yuv-metrics also ssim_yuv_frames_<idx>.npy and ssim_yuv_<idx>.npy, on the two 8-bit "
+                        "clips psnr_yuv compares.  A reported value only: no --policy decides by it")
     return p
 
 
 YUV_FLAGS = ("data_yuv", "yuv_geometry", "yuv_upsample", "yuv_out", "yuv_metrics")
+OPT_IN_FLAGS = YUV_FLAGS + ("ssim",)         # written to args.yml only when used: a run without them leaves what it always left
 
 
 def add_yuv_input_flags(p):
@@ -313,8 +321,8 @@ def main(argv=None):
         with open(os.path.join(vf, "config.yml"), "w") as f:
             yaml.dump(raw, f, default_flow_style=False)
         with open(os.path.join(vf, "args.yml"), "w") as f:
-            defaults = vars(build_parser().parse_args([]))      # the YUV flags appear only when used
-            yaml.dump({k: v for k, v in vars(args).items() if k not in YUV_FLAGS or v != defaults[k]}, f, default_flow_style=False)
+            defaults = vars(build_parser().parse_args([]))      # the YUV flags and --ssim appear only when used
+            yaml.dump({k: v for k, v in vars(args).items() if k not in OPT_IN_FLAGS or v != defaults[k]}, f, default_flow_style=False)
 
     # ---- weights: rank 0 reads (or synthesises) them, one RCCL broadcast each ----
     sd_d, sd_e = None, {}
@@ -360,7 +368,7 @@ def main(argv=None):
     t_start = time.time()
     vids = list(range(args.start_idx + lo, args.start_idx + hi))
 
-    gt_feats, fvd_store, yuv_store = {}, {}, {}
+    gt_feats, fvd_store, yuv_store, ssim_store, ssim_yuv_store = {}, {}, {}, {}, {}
 
     def job_fvds(jobs):
         """FVD of each decoded clip against its video's original, as city_sender.py:575-577 computes it: calculate_fvd of
@@ -392,9 +400,17 @@ def main(argv=None):
         if args.yuv_out:
             from . import video_io as V
             V.write_clip(os.path.join(args.output_path, f"output_{vid}", "city_idx%d_q%d_thr%.2f.y4m" % (vid, q, thr)), x, yuv_fps)
+        if args.ssim:
+            from .ssim import ssim_frames
+            ss = ssim_frames(x, gt)
+            print(f"[rank {rank}] video {vid} q{q} thr {thr:.2f}: SSIM: {np.mean(ss):.5f}", flush=True)
+            ssim_store.setdefault(vid, []).append(ss)
         if args.yuv_metrics:
             from . import video_io as V
-            yuv_store.setdefault(vid, []).append(V.psnr_yuv(x, gt))
+            pair = V.yuv_metric_clips(x, gt)
+            yuv_store.setdefault(vid, []).append(V.psnr_yuv(x, gt, clips=pair))
+            if args.ssim:
+                ssim_yuv_store.setdefault(vid, []).append(V.ssim_yuv(x, gt, clips=pair))
 
     store = {}
     if args.policy == "mask":
@@ -487,6 +503,10 @@ def main(argv=None):
         if vid in yuv_store:     # the codec benchmark's PSNR (bench_uvg.py:487,508-509), laid out as psnr_<idx>.npy
             np.save(os.path.join(out_root, f"psnr_yuv_{vid}.npy"), rd_envelope(bpps, np.mean(np.asarray(yuv_store[vid]), 1), True))
             np.save(os.path.join(out_root, f"psnr_yuv_frames_{vid}.npy"), np.asarray(yuv_store[vid]))
+        for name, kept in (("ssim", ssim_store), ("ssim_yuv", ssim_yuv_store)):      # --ssim: laid out as psnr_<idx>.npy
+            if vid in kept:
+                np.save(os.path.join(out_root, f"{name}_{vid}.npy"), rd_envelope(bpps, np.mean(np.asarray(kept[vid]), 1), True))
+                np.save(os.path.join(out_root, f"{name}_frames_{vid}.npy"), np.asarray(kept[vid]))
         if vid in fvd_store:     # reference name fvd_<idx>.npy: RD envelope [bpp; FVD], lower is better; raw values beside it
             np.save(os.path.join(out_root, f"fvd_{vid}.npy"), rd_envelope(bpps, np.asarray(fvd_store[vid]), False))
             np.save(os.path.join(out_root, f"fvd_values_{vid}.npy"), np.asarray(fvd_store[vid]))

@@ -6,7 +6,7 @@ device raises ``EvcLibraryError`` so a silent eager/CPU substitute can never pas
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_longlong, c_uint, c_uint8, c_ulonglong, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_longlong, c_uint, c_uint8, c_ulonglong, c_void_p
 
 import numpy as np
 import torch
@@ -180,6 +180,9 @@ HIP_SYMBOLS = {
     "evc_noise_normal_f32": (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_ulonglong, c_uint, c_int, c_void_p]),
     "evc_yuv420_to_rgb": (c_int, [c_void_p] + [c_longlong] * 6 + [c_int] * 5 + [c_void_p, c_int, c_void_p]),
     "evc_rgb_to_yuv420": (c_int, [c_void_p, c_void_p] + [c_longlong] * 6 + [c_int] * 4 + [c_void_p, c_void_p]),
+    "evc_ssim_workspace_bytes": (c_longlong, [c_int, c_int, c_int]),
+    "evc_ssim_planes_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_double, c_void_p, c_void_p,
+                                    c_void_p]),
 }
 
 RANS_SYMBOLS = {
@@ -1156,6 +1159,24 @@ def bottleneck_rate(z, C, medians, density, bits=None, out=None):
     _check(hip_lib().evc_bottleneck_rate_f32(fptr(z), ld, C, B, H, W, fptr(medians), fptr(density), fptr(z_hat),
                                              fptr(bits, torch.float64), stream_ptr()), "evc_bottleneck_rate_f32")
     return z_hat, bits
+
+
+def ssim_planes(a, b, taps, c1, c2, out=None):
+    """a, b: (N, H, W) float32 planes in [0, 1]; taps: the 11 window taps, float64 on the device -> out (N,) float64 on the
+    device: the mean of each plane's SSIM map (include/evc_hip.h evc_ssim_planes_f32)."""
+    L = hip_lib()
+    N, H, W = a.shape
+    assert b.shape == a.shape and taps.shape == (11,)
+    if out is None:
+        out = torch.empty((N,), device=a.device, dtype=torch.float64)
+    assert out.shape == (N,)
+    nbytes = L.evc_ssim_workspace_bytes(N, H, W)
+    if nbytes < 0:
+        raise EvcKernelError(f"evc_ssim_workspace_bytes rejected the arguments ({nbytes})")
+    ws = torch.empty((max(1, nbytes // 8),), device=a.device, dtype=torch.float64)
+    _check(L.evc_ssim_planes_f32(fptr(a), fptr(b), N, H, W, fptr(taps, torch.float64), float(c1), float(c2),
+                                 fptr(out, torch.float64), ptr(ws), stream_ptr()), "evc_ssim_planes_f32")
+    return out
 
 
 # ---- host rANS -------------------------------------------------------------------------------

@@ -120,6 +120,8 @@ def build_parser():
     p.add_argument("--yuv", action="store_true",
                    help="also write decoded_v<vid>_q<q>_thr<thr>.y4m (8-bit 4:2:0, full-range BT.709) beside each .npy")
     p.add_argument("--fps", type=str, default="30", help="--yuv: frame rate of the written files (30, 29.97 or 30000/1001)")
+    p.add_argument("--ssim", action="store_true",
+                   help="when the original clips are present, also print each job's SSIM (city_sender.py --ssim) after its PSNR")
     return p
 
 
@@ -179,6 +181,9 @@ def main(argv=None):
         if data is not None:
             gt = np.asarray(data[job["vid"]], dtype=np.float32) / 255.0
             line += " PSNR %.3f" % np.mean([cli.cal_psnr(x[t], gt[t]) for t in range(len(x))])
+            if args.ssim:
+                from .ssim import ssim_frames
+                line += " SSIM %.5f" % np.mean(ssim_frames(np.ascontiguousarray(x, dtype=np.float32), gt[:len(x)]))
         same = frames_match(job, x)
         if same is not None:             # format 4: the receiver's frames against the sender's checksum
             line += ", frames: match" if same else ", frames: MISMATCH"

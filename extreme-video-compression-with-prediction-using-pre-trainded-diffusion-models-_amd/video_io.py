@@ -322,6 +322,20 @@ def psnr_u8(a, b):
         return 10 * np.log10(255.0 ** 2 / mse)
 
 
-def psnr_yuv(x, gt):
-    """The PSNR of the reference's codec benchmark for a decoded clip x against its original gt (both (T, 3, H, W) in [0, 1])."""
-    return psnr_u8(yuv_round_trip_u8(gt), yuv_round_trip_u8(x))
+def yuv_metric_clips(x, gt):
+    """The two clips the reference's codec benchmark compares for a decoded clip x against its original gt (both (T, 3, H, W)
+    in [0, 1]): (original, decoded), each through ``yuv_round_trip_u8``."""
+    return yuv_round_trip_u8(gt), yuv_round_trip_u8(x)
+
+
+def psnr_yuv(x, gt, clips=None):
+    """The PSNR of the reference's codec benchmark for a decoded clip x against its original gt (both (T, 3, H, W) in [0, 1]).
+    ``clips``: ``yuv_metric_clips(x, gt)`` when the caller already holds them."""
+    return psnr_u8(*(clips if clips is not None else yuv_metric_clips(x, gt)))
+
+
+def ssim_yuv(x, gt, clips=None):
+    """Per-frame SSIM (ssim.py) on the same two 8-bit-rounded RGB clips ``psnr_yuv`` compares, scaled to [0, 1]."""
+    from .ssim import ssim_frames
+    a, b = clips if clips is not None else yuv_metric_clips(x, gt)
+    return ssim_frames(b.astype(np.float32) / np.float32(255.0), a.astype(np.float32) / np.float32(255.0))

@@ -537,6 +537,22 @@ int evc_rgb_to_yuv420(const float* rgb, unsigned char* dst, long long dst_bytes,
                       long long off_y, long long off_u, long long off_v, int N, int H, int W, int bits, unsigned* events,
                       void* stream);
 
+/* ---- SSIM: the structural similarity of the reference's metric helpers (csrc/ssim.hip) ------
+ * ssim() of fvd_utils/calculate_ssim.py:6-23 for N pairs of planes.  a, b: N contiguous planes of H x W fp32 each, values
+ * in [0, 1]; taps11: the 11 window taps in float64 ON THE DEVICE (the host computes cv2.getGaussianKernel(11, 1.5)); c1, c2:
+ * the stabilisers (0.01^2, 0.03^2 in the reference); out[N]: the mean of each plane's SSIM map over the valid region
+ * (H - 10) x (W - 10).  The inputs are widened to double and everything after that is double: the separable filter (11 taps
+ * along a row, then 11 along a column) of x1, x2, x1^2, x2^2, x1 x2, the map ((2 mu1 mu2 + c1)(2 s12 + c2)) / ((mu1^2 + mu2^2
+ * + c1)(s1 + s2 + c2)) with s = E[.] - mu mu, evaluated operation by operation, and its sum.  The filtered maps stay on
+ * the chip; per-tile sums go to ws (evc_ssim_workspace_bytes(N, H, W) bytes, 8-byte aligned) and are added per plane in a
+ * fixed order by a second launch: a plane's value depends on its own samples and (H, W) only, bit for bit -- not on N, on
+ * its place in the batch or on the other planes.  Nothing is clamped or dropped: a NaN or an infinity in a plane makes that
+ * plane's value NaN and touches no other plane.  EVC_EINVAL for H < 11, W < 11, N < 0 or (N > 0) a NULL pointer; N == 0
+ * launches nothing and returns EVC_OK.  N * H * W may exceed 2^31. */
+long long evc_ssim_workspace_bytes(int N, int H, int W);
+int evc_ssim_planes_f32(const float* a, const float* b, int N, int H, int W, const double* taps11, double c1, double c2,
+                        double* out, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
