@@ -22,6 +22,9 @@ as ``.y4m`` and ``--yuv-metrics`` adds the PSNR of the reference's codec benchma
 (``ElicModel.estimate``) instead of the length of range-coded strings: same frames, fractional bits.
 ``--ssim`` adds the reference's SSIM (fvd_utils/calculate_ssim.py; ssim.py, csrc/ssim.hip) of every job:
 one more printed line and ``ssim_<idx>.npy`` / ``ssim_frames_<idx>.npy``; a reported value, never a decision rule.
+``--lpips NET:BACKBONE.pth,LIN.pth`` adds the benchmark's LPIPS (fvd_utils/calculate_lpips.py; lpips.py ``Lpips``, DESIGN.md section
+8e) of every job on the alex, vgg or squeeze backbone: one more printed line and ``lpips_<net>_<idx>.npy`` /
+``lpips_<net>_frames_<idx>.npy``; ``--lpips-net`` picks the backbone of the ``--policy lpips`` rule (default alex).
 """
 import argparse
 import os
@@ -129,11 +132,20 @@ def build_parser():
                         "float64, mean over the valid region and the 3 channels) and save ssim_frames_<idx>.npy (jobs, 30) and "
                         "ssim_<idx>.npy; with --yuv-metrics also ssim_yuv_frames_<idx>.npy and ssim_yuv_<idx>.npy, on the two 8-bit "
                         "clips psnr_yuv compares.  A reported value only: no --policy decides by it")
+    p.add_argument("--lpips-net", choices=["alex", "vgg", "squeeze"], default="alex",
+                   help="lpips policy: the backbone whose weight files --metric names (the HIP LPIPS family, lpips.py); frames are "
+                        "passed to it as they are, as with the default")
+    p.add_argument("--lpips", type=str, default=None, metavar="NET:BACKBONE.pth,LIN.pth",
+                   help="also report each job's LPIPS against the original clip as the reference's benchmark computes it "
+                        "(fvd_utils/calculate_lpips.py:9-58: frames mapped to [-1, 1], spatial map, its mean), under any --policy: "
+                        "NET = alex, vgg or squeeze, then torchvision's checkpoint of the backbone and lpips' weights/v0.1/NET.pth, "
+                        "or NET:ONE_SAVED_STATE_DICT.pth; prints one LPIPS(NET): line per job and saves lpips_NET_frames_<idx>.npy "
+                        "(jobs, 30) and lpips_NET_<idx>.npy (RD envelope, lower is better)")
     return p
 
 
 YUV_FLAGS = ("data_yuv", "yuv_geometry", "yuv_upsample", "yuv_out", "yuv_metrics")
-OPT_IN_FLAGS = YUV_FLAGS + ("ssim",)         # written to args.yml only when used: a run without them leaves what it always left
+OPT_IN_FLAGS = YUV_FLAGS + ("ssim", "lpips", "lpips_net")       # written to args.yml only when used: a run without them leaves what it always left
 
 
 def add_yuv_input_flags(p):
@@ -266,6 +278,9 @@ def main(argv=None):
     if args.entropy_estimation and args.bitstream_dir:
         sys.exit("--entropy-estimation with --bitstream-dir: an estimated rate comes without coded strings, so there is nothing "
                  "to write into a bitstream; drop one of the two")
+    if args.lpips:
+        from .lpips import parse_spec
+        parse_spec(args.lpips)           # FileNotFoundError names a missing weight file before any GPU work
     import yaml
     from . import dist as D
     if D.needs_self_launch(args.gpus):      # parent: starts the ranks before any HIP call, relays their exit status
@@ -313,6 +328,10 @@ def main(argv=None):
     if fvd_path:
         from . import fvd as FV
         i3d = FV.I3d.from_file(fvd_path, device=device)
+    lp = None
+    if args.lpips:
+        from .lpips import Lpips
+        lp = Lpips.from_spec(args.lpips, device=device)
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     vf = os.path.join(args.exp, "video_samples", args.video_folder)
@@ -368,7 +387,7 @@ def main(argv=None):
     t_start = time.time()
     vids = list(range(args.start_idx + lo, args.start_idx + hi))
 
-    gt_feats, fvd_store, yuv_store, ssim_store, ssim_yuv_store = {}, {}, {}, {}, {}
+    gt_feats, fvd_store, yuv_store, ssim_store, ssim_yuv_store, lpips_store = {}, {}, {}, {}, {}, {}
 
     def job_fvds(jobs):
         """FVD of each decoded clip against its video's original, as city_sender.py:575-577 computes it: calculate_fvd of
@@ -405,6 +424,11 @@ def main(argv=None):
             ss = ssim_frames(x, gt)
             print(f"[rank {rank}] video {vid} q{q} thr {thr:.2f}: SSIM: {np.mean(ss):.5f}", flush=True)
             ssim_store.setdefault(vid, []).append(ss)
+        if lp is not None:           # the benchmark's LPIPS (calculate_lpips.py:35-58), one value per frame
+            lv = lp.spatial_mean(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)),
+                                 torch.from_numpy(np.ascontiguousarray(gt, dtype=np.float32))).double().cpu().numpy()
+            print(f"[rank {rank}] video {vid} q{q} thr {thr:.2f}: LPIPS({lp.net}): {np.mean(lv):.5f}", flush=True)
+            lpips_store.setdefault(vid, []).append(lv)
         if args.yuv_metrics:
             from . import video_io as V
             pair = V.yuv_metric_clips(x, gt)
@@ -459,7 +483,7 @@ def main(argv=None):
         # city_sender.py:495-607 batched (policy.py): every (video, q, threshold) job of this rank advances in lockstep,
         # `--policy-batch` jobs per score-network launch; key frames coded once per (video, q, frame).
         from . import policy as P
-        metric = P.load_metric(args.policy, args.metric, device)
+        metric = P.load_metric(args.policy, args.metric, device, net=args.lpips_net)
         dec = ClipDecoder(net, None, cfg, S.get_sampler(args.sampler), range_recovery=args.range_recovery,
                           log=lambda m: print(f"[rank {rank}] {m}", flush=True))
         clips = {vid: torch.from_numpy(np.asarray(data[vid], dtype=np.float32) / 255.0) for vid in vids}
@@ -507,6 +531,10 @@ def main(argv=None):
             if vid in kept:
                 np.save(os.path.join(out_root, f"{name}_{vid}.npy"), rd_envelope(bpps, np.mean(np.asarray(kept[vid]), 1), True))
                 np.save(os.path.join(out_root, f"{name}_frames_{vid}.npy"), np.asarray(kept[vid]))
+        if vid in lpips_store:   # --lpips NET:...: laid out as psnr_<idx>.npy, lower is better
+            np.save(os.path.join(out_root, f"lpips_{lp.net}_{vid}.npy"),
+                    rd_envelope(bpps, np.mean(np.asarray(lpips_store[vid]), 1), False))
+            np.save(os.path.join(out_root, f"lpips_{lp.net}_frames_{vid}.npy"), np.asarray(lpips_store[vid]))
         if vid in fvd_store:     # reference name fvd_<idx>.npy: RD envelope [bpp; FVD], lower is better; raw values beside it
             np.save(os.path.join(out_root, f"fvd_{vid}.npy"), rd_envelope(bpps, np.asarray(fvd_store[vid]), False))
             np.save(os.path.join(out_root, f"fvd_values_{vid}.npy"), np.asarray(fvd_store[vid]))

@@ -87,6 +87,10 @@ HIP_SYMBOLS = {
     "evc_im2col_nchw_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_void_p, c_void_p]),
     "evc_maxpool3s2_nhwc_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "evc_lpips_layer_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "evc_maxpool2d_nhwc_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
+    "evc_lpips_map_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "evc_lpips_map_mean_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "evc_lpips_upsample_add_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     "evc_i3d_stem_im2col_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 17 + [c_void_p]),
     "evc_maxpool3d_same_nthwc_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 11 + [c_void_p]),
     "evc_i3d_head_f32": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
@@ -443,6 +447,54 @@ def lpips_layer(f0, f1, lin_w, dist, accumulate):
     _check(hip_lib().evc_lpips_layer_f32(fptr(f0), fptr(f1), fptr(lin_w), fptr(dist), N, H * W, C, int(bool(accumulate)),
                                          stream_ptr()), "evc_lpips_layer_f32")
     return dist
+
+
+def pool_out_size(size, k, stride, ceil_mode):
+    """torch's pooling output size without padding: in ceil mode the last window must start inside the input."""
+    num = size - k + (stride - 1 if ceil_mode else 0)
+    if num < 0:
+        raise ValueError(f"max pool {k} stride {stride} of a side of {size}: no output")
+    o = num // stride + 1
+    return o - 1 if ceil_mode and (o - 1) * stride >= size else o
+
+
+def maxpool2d_nhwc(x, k, stride, ceil_mode=False):
+    """MaxPool2d(k, stride, ceil_mode=...) without padding, k in {2, 3}; x: (N, H, W, C), C % 4 == 0 (include/evc_hip.h)."""
+    N, H, W, C = x.shape
+    out = torch.empty((N, pool_out_size(H, k, stride, ceil_mode), pool_out_size(W, k, stride, ceil_mode), C), device=x.device,
+                      dtype=torch.float32)
+    _check(hip_lib().evc_maxpool2d_nhwc_f32(fptr(x), fptr(out), N, H, W, C, k, stride, int(bool(ceil_mode)), stream_ptr()),
+           "evc_maxpool2d_nhwc_f32")
+    return out
+
+
+def lpips_map(f0, f1, lin_w, out=None):
+    """(N, H, W) per-pixel distances of one tap: lin_w . (unit-normalised f0 - unit-normalised f1)^2; f0, f1: (N, H, W, C)."""
+    N, H, W, C = f0.shape
+    assert f1.shape == f0.shape and lin_w.numel() == C
+    if out is None:
+        out = torch.empty((N, H, W), device=f0.device, dtype=torch.float32)
+    assert out.numel() == N * H * W
+    _check(hip_lib().evc_lpips_map_f32(fptr(f0), fptr(f1), fptr(lin_w), fptr(out), N, H * W, C, stream_ptr()), "evc_lpips_map_f32")
+    return out
+
+
+def lpips_map_mean(m, dist, accumulate):
+    """dist[n] (+)= mean of m[n]; m: (N, H, W) or (N, HW)."""
+    N = m.shape[0]
+    assert dist.numel() == N
+    _check(hip_lib().evc_lpips_map_mean_f32(fptr(m), fptr(dist), N, m.numel() // N, int(bool(accumulate)), stream_ptr()),
+           "evc_lpips_map_mean_f32")
+    return dist
+
+
+def lpips_upsample_add(m, out, accumulate):
+    """out[n] (+)= bilinear(m[n], size=out.shape[1:], align_corners=False); m: (N, h, w), out: (N, H, W)."""
+    N, h, w = m.shape
+    assert out.shape[0] == N and out.dim() == 3
+    _check(hip_lib().evc_lpips_upsample_add_f32(fptr(m), fptr(out), N, h, w, out.shape[1], out.shape[2], int(bool(accumulate)),
+                                                stream_ptr()), "evc_lpips_upsample_add_f32")
+    return out
 
 
 def same_pad(size, k, s):

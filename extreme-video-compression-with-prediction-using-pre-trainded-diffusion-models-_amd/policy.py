@@ -71,11 +71,12 @@ class CallableMetric:
         return value <= thr
 
 
-def load_metric(policy, spec=None, device="cuda"):
+def load_metric(policy, spec=None, device="cuda", net="alex"):
     """``psnr`` -> PsnrMetric; ``lpips`` -> the HIP LPIPS-AlexNet (``lpips.LpipsAlex``) when ``spec`` names its weight files
     ("alexnet.pth,alex.pth" or one saved LPIPS state dict), else a CallableMetric around ``spec`` = "package.module:callable"
     (called as fn(pred, gt)), or around the ``lpips`` package (LPIPS(net='alex'), inputs scaled to [-1, 1] as lpips expects --
-    the reference feeds [0, 1] frames unnormalised, city_sender.py:389-390; pass your own callable to reproduce that)."""
+    the reference feeds [0, 1] frames unnormalised, city_sender.py:389-390; pass your own callable to reproduce that).
+    ``net`` = "vgg" / "squeeze" (``--lpips-net``): the weight files are that backbone's, and the rule runs on ``lpips.Lpips``."""
     if policy == "psnr":
         return PsnrMetric()
     if policy != "lpips":
@@ -84,7 +85,12 @@ def load_metric(policy, spec=None, device="cuda"):
         spec = spec[5:] if spec.startswith("file:") else spec
         # weight files: "alexnet-owt-*.pth,alex.pth" (torchvision backbone + lpips v0.1 linear layers) or one file holding
         # a saved lpips.LPIPS state dict -> the HIP implementation (lpips.py); frames are passed as they are, like the reference
-        from .lpips import LpipsAlex
+        from .lpips import NETS, Lpips, LpipsAlex
+        if net not in NETS:
+            raise ValueError(f"unknown LPIPS network {net!r}: one of {', '.join(NETS)}")
+        if net != "alex":
+            other = Lpips.from_spec(spec, net, device)
+            return CallableMetric(lambda a, b: other(a, b), name=f"lpips-{net}-hip")
         paths = spec.split(",")
         net = (LpipsAlex.from_files(paths[0], paths[1], device) if len(paths) == 2 else
                LpipsAlex(torch.load(paths[0], map_location="cpu", weights_only=True), device))

@@ -122,12 +122,18 @@ def build_parser():
     p.add_argument("--fps", type=str, default="30", help="--yuv: frame rate of the written files (30, 29.97 or 30000/1001)")
     p.add_argument("--ssim", action="store_true",
                    help="when the original clips are present, also print each job's SSIM (city_sender.py --ssim) after its PSNR")
+    p.add_argument("--lpips", type=str, default=None, metavar="NET:BACKBONE.pth,LIN.pth",
+                   help="when the original clips are present, also print each job's LPIPS (city_sender.py --lpips: NET = alex, vgg "
+                        "or squeeze; frames mapped to [-1, 1], mean of the spatial map) after its PSNR / SSIM")
     return p
 
 
 def main(argv=None):
     from . import ckpt, cli, config as C, lib as L, synthetic
     args = cli.parse_args(argv, build_parser())
+    if args.lpips:
+        from .lpips import parse_spec
+        parse_spec(args.lpips)           # FileNotFoundError names a missing weight file before any GPU work
     from .elic import ElicModel
     from .scorenet import build_score_network
     paths = args.paths or cli.DEFAULT_PATHS
@@ -146,6 +152,10 @@ def main(argv=None):
     else:
         sys.exit(f"missing {ck} (pass --synthetic for seeded stand-in weights)")
     net = build_score_network(cfg, sd_d, device=device)
+    lp = None
+    if args.lpips:
+        from .lpips import Lpips
+        lp = Lpips.from_spec(args.lpips, device=device)
 
     def model_for(q):
         if q < len(paths) and os.path.exists(paths[q]):
@@ -184,6 +194,9 @@ def main(argv=None):
             if args.ssim:
                 from .ssim import ssim_frames
                 line += " SSIM %.5f" % np.mean(ssim_frames(np.ascontiguousarray(x, dtype=np.float32), gt[:len(x)]))
+            if lp is not None:
+                v = lp.spatial_mean(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)), torch.from_numpy(gt[:len(x)]))
+                line += " LPIPS(%s) %.5f" % (lp.net, float(v.double().mean()))
         same = frames_match(job, x)
         if same is not None:             # format 4: the receiver's frames against the sender's checksum
             line += ", frames: match" if same else ", frames: MISMATCH"

@@ -457,6 +457,35 @@ int evc_maxpool3s2_nhwc_f32(const float* x, float* out, int N, int H, int W, int
 int evc_lpips_layer_f32(const float* f0, const float* f1, const float* lin_w, float* dist, int N, int HW, int C, int accumulate,
                         void* stream);
 
+/* ---- LPIPS, the whole family: VGG16 and SqueezeNet 1.1 backbones, spatial maps (csrc/lpips.hip) ----
+ * The reference vendors all three networks (models/networks_basic.py:25-88 PNetLin with pnet_type vgg / alex / squeeze,
+ * models/pretrained_networks.py:5-134 the slices, weights/v0.1/{alex,vgg,squeeze}.pth the trained linear layers) and its
+ * benchmark metric is the spatial form (fvd_utils/calculate_lpips.py:9-58: lpips.LPIPS(net=..., spatial=True) on frames in
+ * [-1, 1], .mean() of the map).  The convolutions run on evc_conv2d_nhwc_f32 and evc_im2col_nchw_f32; these are the rest:
+ *   evc_maxpool2d_nhwc_f32   MaxPool2d(k, stride) without padding, k in {2, 3}: (2, 2) floor of torchvision vgg16.features
+ *                         4/9/16/23 and (3, 2, ceil_mode=True) of squeezenet1_1.features 2/5/8 (pretrained_networks.py:5-53,96-134).
+ *                         (N, H, W, C) -> (N, Ho, Wo, C) with torch's output size: floor or ceil of (H - k) / stride, + 1, and
+ *                         in ceil mode one less when the last window would start beyond the input.  Window elements beyond
+ *                         the input are skipped; a NaN is kept as torch keeps it.  C % 4 == 0 (16-byte accesses); H, W >= k, or in ceil mode >= k - stride + 1.
+ *   evc_lpips_map_f32     map[n][p] = sum_c lin_w[c] * (f0/(|f0|_2 + 1e-10) - f1/(|f1|_2 + 1e-10))^2 for every pixel p of every
+ *                         pair n (networks_basic.py:68-70 + NetLinLayer :100-107, eval_models.py:35-37); f0, f1: (N, HW, C)
+ *                         NHWC, 16-byte aligned like lin_w, C a multiple of 64 from 64 to 512.  The grid runs over all N * HW
+ *                         pixels, 16 lanes per pixel; each element is read once.  A NaN / inf channel makes its pixel NaN.
+ *   evc_lpips_map_mean_f32   dist[n] (+)= mean_p map[n][p] (spatial_average, networks_basic.py:15-16); the summation order
+ *                         depends on HW only.
+ *   evc_lpips_upsample_add_f32   out[n] (+)= bilinear(map[n] (h, w) -> (H, W)), align_corners = False, torch's float32 formula:
+ *                         scale = h / H, source index max((dst + 0.5) * scale - 0.5, 0), upper neighbour clamped to h - 1.
+ *                         lpips 0.1.4 (requirements.txt:66) up-samples with nn.Upsample(size=(H, W)); the vendored
+ *                         networks_basic.py:18-22 passes scale_factor = H / h instead, which is the same map wherever that
+ *                         form gives an (H, W) output at all, up to the rounding of 1 / (H / h) against h / H.  NaN and inf
+ *                         propagate as in torch (a zero weight times inf is NaN).
+ * accumulate: 0 stores, 1 adds to what dist / out hold.  EVC_EINVAL before any launch for a null pointer, a size <= 0, a
+ * channel count or k outside the above. */
+int evc_maxpool2d_nhwc_f32(const float* x, float* out, int N, int H, int W, int C, int k, int stride, int ceil_mode, void* stream);
+int evc_lpips_map_f32(const float* f0, const float* f1, const float* lin_w, float* map, int N, int HW, int C, void* stream);
+int evc_lpips_map_mean_f32(const float* map, float* dist, int N, int HW, int accumulate, void* stream);
+int evc_lpips_upsample_add_f32(const float* map, float* out, int N, int h, int w, int H, int W, int accumulate, void* stream);
+
 /* ---- I3D (InceptionI3d(400), the feature network of the Frechet video distance) ----------------------------------
  * Replaces the detector of calculate_fvd (city_sender.py:264-279, called per job at :575-589): preprocess_single
  * (models/fvd/fvd.py: bilinear resize, align_corners=False, of the shorter side to R = 224, the other side ceil-ed, centre
