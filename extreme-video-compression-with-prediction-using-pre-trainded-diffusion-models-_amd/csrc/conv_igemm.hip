@@ -2027,9 +2027,13 @@ static int conv_validate(const evc_conv_args* a) {
 // of 128 pixels: the 8x8 layers) use the 64-pixel tile (TM = 1) first: half the split factor means half the slab
 // write + combine traffic and no half-empty tiles (A/B: 8x8 768->768 58 -> 69 TFLOP/s; on mid-size grids such
 // as 32x32 576->576 the smaller tile loses, 92 -> 84, so it is not used there).
-struct TileCfg { int tm, tn, bm, bn; long long tiles; int splits; int reuse; int wide; int steps_per_split;
-                 int tail_first, tail_tiles, tail_splits, tail_sps;       // K-split tail: pixel tiles >= tail_first (0 tiles = none)
-                 int cut_chunk; };                                        // wide kernel, 2 UNEQUAL K pieces: [0, cut) | [cut, nchunk); 0 = equal
+// TileCfg is the geometry half of a launch, picked by conv_tile_cfg(); conv_resolve() below calls that ONCE per entry point and
+// adds the rest (load mode, kernel instance, grid, LDS, moment runs, workspace, refusals): one ConvLaunch that everyone reads.
+struct TileCfg { int tm, tn, bm, bn; long long tiles; int splits = 1; int reuse = 0; int wide = 0; int steps_per_split;
+                 int tail_first = 0, tail_tiles = 0, tail_splits = 1, tail_sps = 0;   // K-split tail: pixel tiles >= tail_first (0 tiles = none)
+                 int cut_chunk = 0;                                       // wide kernel, 2 UNEQUAL K pieces: [0, cut) | [cut, nchunk); 0 = equal
+                 // conv_wide_kernel's geometry on a grid of `wgs` 256 x 192 tiles: no tail, no cut until the caller adds one
+                 void set_wide(long long wgs) { *this = TileCfg(); wide = 1; tm = 4; tn = 3; bm = 256; bn = 192; tiles = wgs; } };
 static int g_wide_cut = 1;     // run-time option "wide_cut": the unequal 2-way K split of conv_wide_kernel on grids of 129..255 workgroups
 static int g_tail_split = EVC_CONV_TAIL;   // run-time option "tail_split"
 static int g_wide_tiles = EVC_SPLIT_WIDE_TILES;   // harness A/B switch for the 256-pixel row-reuse tiles
@@ -2064,7 +2068,6 @@ static void split_tile_cfg(const evc_conv_args* a, long long M, long long ntile,
     };
     double best = 1e300;
     int best_tm = 2, best_s = 1;
-    c.tail_first = 0; c.tail_tiles = 0; c.tail_splits = 1; c.tail_sps = 0;
     for (int tm = 2; tm >= 1; --tm) {
         if (!inv && g_force_tm && tm != g_force_tm) continue;
         const long long tiles = ((M + 64 * tm - 1) / (64 * tm)) * ntile;
@@ -2139,15 +2142,12 @@ static bool wide_ok(const evc_conv_args* a, bool inv) {
 // A/B switches are ignored (the plan must be a function of the layer alone), no K-split tail, no 256-pixel row-reuse form.
 static TileCfg conv_tile_cfg_at(const evc_conv_args* a, bool inv) {
     TileCfg c;
-    c.wide = 0;
-    c.cut_chunk = 0;
     const long long M = (long long)a->B * a->H * a->W;
     const int CoPad = evc_conv_co_pad(a->Co);
     c.tn = pick_tn(CoPad);
     c.bn = 64 * c.tn;
     const long long ntile = CoPad / c.bn;
     const int nsteps = a->KH * a->KW * ((a->C0 + a->C1) / KC);
-    c.reuse = 0;
     if (is_split_arith(a->arith)) {
         const int np = arith_planes(a->arith);
         // row-reuse kernel: 3x3 filters, 128-pixel tiles made of whole image rows (and an LDS image that fits: W >= 4)
@@ -2166,7 +2166,6 @@ static TileCfg conv_tile_cfg_at(const evc_conv_args* a, bool inv) {
             }
         }
     } else {
-        c.tail_first = 0; c.tail_tiles = 0; c.tail_splits = 1; c.tail_sps = 0;
         c.tm = (!EVC_CONV_TM1 || ((M + 127) / 128) * ntile >= 64) ? 2 : 1;
         if (g_force_tm && !inv) c.tm = g_force_tm;
         c.bm = 64 * c.tm;
@@ -2189,8 +2188,7 @@ static TileCfg conv_tile_cfg_at(const evc_conv_args* a, bool inv) {
         const long long tm_all = M / 256, nt = a->Co / 192, wgs = tm_all * nt;
         if (wgs >= 256) {
             const int nchunk = (a->C0 + a->C1) / KC;
-            c.wide = 1; c.reuse = 0; c.tm = 4; c.tn = 3; c.bm = 256; c.bn = 192; c.tiles = wgs; c.splits = 1;
-            c.tail_first = 0; c.tail_tiles = 0; c.tail_splits = 1; c.tail_sps = 0;
+            c.set_wide(wgs);
             const long long Rr = wgs / 256;
             const long long main_m = Rr * 256 / nt, tail_m = tm_all - main_m;
             if (!inv && g_tail_split && tail_m > 0) {
@@ -2222,8 +2220,7 @@ static TileCfg conv_tile_cfg_at(const evc_conv_args* a, bool inv) {
             // take it when a reasonable share of the machine is busy: below that the many-small-workgroups kernel wins
             if (best_s > 0 && wgs * best_s >= 128) {
                 const int cps = (nchunk + best_s - 1) / best_s;
-                c.wide = 1; c.reuse = 0; c.tm = 4; c.tn = 3; c.bm = 256; c.bn = 192; c.tiles = wgs;
-                c.tail_first = 0; c.tail_tiles = 0; c.tail_splits = 1; c.tail_sps = 0;
+                c.set_wide(wgs);
                 c.splits = (nchunk + cps - 1) / cps;
                 c.steps_per_split = cps * 9;
                 // 129..255 unsplit workgroups (64 x 64 x 192 channels at B = 9: 144): two UNEQUAL pieces per tile.  The long
@@ -2287,75 +2284,95 @@ extern "C" int evc_conv_set_option(const char* name, int value) {
     return EVC_EINVAL;
 }
 
-// The fused 1x1 operand exists in the f16x3 row-reuse kernel only (3x3 filters on tiles of whole image rows).
-extern "C" int evc_conv_fused_1x1_supported(const evc_conv_args* a) {
-    if (conv_validate(a) != EVC_OK) return 0;
-    if (a->arith != EVC_ARITH_F16X3 || a->KH != 3 || a->KW != 3) return 0;
-    const TileCfg c = conv_tile_cfg(a);
-    // batch-invariant mode: the fused operand's scale is per sample and tile-uniform in these kernels: whole tiles per sample
-    if (a->invariant && ((long long)a->H * a->W) % c.bm != 0) return 0;
-    return (c.reuse == 1 || c.wide) ? 1 : 0;
-}
+// Everything that is decided about a launch before it happens, resolved ONCE per entry point by conv_resolve(): the queries
+// and the launch read this struct and nothing else plans.  (No cache: the evc_conv_set_option switches are mutable.)
+enum ConvFamily { FAM_SPLIT3, FAM_SPLIT2, FAM_IGEMM, FAM_RR, FAM_WIDE };
+struct ConvLaunch {
+    int mode;                      // MODE_*: the transform on load
+    ConvFamily family;             // bf16x6 pipelined / f16x3 simple / f32 / row-reuse / wide
+    int np, tm, tn, nu, x2;        // the instance's template arguments (tm: TM, or WM of the row-reuse kernel); 0 where it has none
+    TileCfg cfg;
+    dim3 grid, block;
+    size_t lds;                    // dynamic LDS bytes
+    int stats_runs;                // pixel runs per image of the fused moments (evc_conv_stats_splits), 0 = none are produced
+    long long ws_bytes;            // split-K slabs
+    int fused_1x1;                 // this plan can carry a fused 1x1 operand
+    ConvK k;                       // the kernel's argument, all but the operands (conv_operands() adds them)
+};
 
-// The kernel template instance evc_conv2d_nhwc_f32 launches for these arguments, as rocprofv3 --kernel-trace prints it
-// (without the namespace), e.g. "conv_wide_kernel<2, 4, false>".  Returns the length, or EVC_EINVAL.
-extern "C" int evc_conv_kernel_name(const evc_conv_args* a, char* buf, int n) {
-    if (!buf || n <= 0 || conv_validate(a) != EVC_OK) return EVC_EINVAL;
-    int mode;
-    if (a->coef_a) mode = a->act_in == EVC_ACT_SILU ? MODE_AFFINE_SILU : MODE_AFFINE;
-    else mode = a->act_in == EVC_ACT_SILU ? MODE_SILU : a->act_in == EVC_ACT_RELU ? MODE_RELU : MODE_PLAIN;
-    const TileCfg c = conv_tile_cfg(a);
-    int len;
-    if (c.wide) len = snprintf(buf, n, "conv_wide_kernel<%d, %d, %s>", mode, a->W == 128 ? 4 : 3, a->x2_w_packed ? "true" : "false");
-    else if (is_split_arith(a->arith)) {
-        const int np = arith_planes(a->arith);
-        if (c.reuse) len = snprintf(buf, n, "conv_split_rr_kernel<%d, %d, %d, %d>", np, c.bm == 256 ? 4 : 2, c.tn, mode);
-        else if (np == 3) len = snprintf(buf, n, "conv_split_kernel<%d, %d, %d>", c.tm, c.tn, mode);
-        else len = snprintf(buf, n, "conv_splitn_kernel<2, %d, %d, %d>", c.tm, c.tn, mode);
-    } else len = snprintf(buf, n, "conv_igemm_kernel<%d, %d, %d>", c.tm, c.tn, mode);
-    return len;
-}
+// Fills `p` for `a`.  Returns what the launch returns for these arguments before it touches the device: EVC_OK or the refusal.
+static int conv_resolve(const evc_conv_args* a, ConvLaunch& p) {
+    const int rc = conv_validate(a);
+    if (rc != EVC_OK) return rc;
+    if (a->coef_a) {
+        if (a->act_in == EVC_ACT_SILU) p.mode = MODE_AFFINE_SILU;
+        else if (a->act_in == EVC_ACT_NONE) p.mode = MODE_AFFINE;
+        else return EVC_EUNSUPPORTED;
+    } else {
+        p.mode = a->act_in == EVC_ACT_SILU ? MODE_SILU : a->act_in == EVC_ACT_RELU ? MODE_RELU : MODE_PLAIN;
+        if (a->act_in != EVC_ACT_NONE && a->act_in != EVC_ACT_SILU && a->act_in != EVC_ACT_RELU) return EVC_EINVAL;
+    }
+    if (a->in_bound && a->arith != EVC_ARITH_F16X3) return EVC_EINVAL;        // only the fp16 split scales its input
+    ConvK& k = p.k;
+    k.C0 = a->C0; k.C1 = a->C1;
+    k.ld0 = a->ld0 > 0 ? a->ld0 : a->C0; k.ld1 = a->ld1 > 0 ? a->ld1 : (a->C1 > 0 ? a->C1 : k.ld0);
+    k.B = a->B; k.H = a->H; k.W = a->W; k.Co = a->Co; k.CoPad = evc_conv_co_pad(a->Co); k.KH = a->KH; k.KW = a->KW;
+    k.M = a->B * a->H * a->W; k.HW = a->H * a->W;
+    // 32-bit byte offsets inside the kernel: each source must stay below 4 GiB
+    if ((long long)k.M * k.ld0 * 4 >= (1LL << 32) || (long long)k.M * k.ld1 * 4 >= (1LL << 32)) return EVC_EUNSUPPORTED;
+    if (a->KH * a->KW > 32) return EVC_EUNSUPPORTED;   // tap-valid bit mask is 32 bits wide
+    k.nchunk = (a->C0 + a->C1) / KC; k.nsteps = a->KH * a->KW * k.nchunk;
+    const TileCfg& c = p.cfg = conv_tile_cfg(a);
+    k.splits = c.splits; k.steps_per_split = c.steps_per_split; k.cut_chunk = c.cut_chunk;
+    k.tail_first = c.tail_tiles ? c.tail_first : 0x7fffffff; k.tail_splits = c.tail_splits; k.tail_sps = c.tail_sps;
+    k.tail_rows = c.tail_tiles * c.bm;
 
-extern "C" int evc_conv_choose_splits(const evc_conv_args* a) {
-    if (conv_validate(a) != EVC_OK) return EVC_EINVAL;
-    return conv_tile_cfg(a).splits;
-}
-
-extern "C" int evc_conv_stats_splits(const evc_conv_args* a) {
-    if (conv_validate(a) != EVC_OK) return 0;
-    const int HW = a->H * a->W;
-    if (HW % 64 != 0) return 0;
-    const TileCfg c = conv_tile_cfg(a);
-    if (c.splits > 1 || c.wide) return HW / 64;                // split-K combine kernel / wide kernel's epilogue: 64-pixel runs
+    if (k.HW % 64 != 0) p.stats_runs = 0;
+    else if (c.splits > 1 || c.wide) p.stats_runs = k.HW / 64;  // split-K combine kernel / wide kernel's epilogue: 64-pixel runs
     // batch-invariant mode: one producer and one run length per layer at every batch.  The epilogue only produces moments
     // from full tiles, and whether the last tile is full depends on the batch unless tiles are whole fractions of a sample.
-    if (a->invariant && HW % c.bm != 0) return 0;
+    else if (a->invariant && k.HW % c.bm != 0) p.stats_runs = 0;
     // (a K-split tail mixes both producers: the epilogue of the unsplit tiles and the combine of the tail write the same
     // 64-pixel runs, the checks below hold for it because its tiles are full 128-pixel tiles)
-    const long long M = (long long)a->B * HW;
-    const int CoPad = evc_conv_co_pad(a->Co);
-    if (M % c.bm != 0 || a->Co != CoPad || a->Co % c.bn != 0) return 0;
-    return HW / (32 * c.tm);                                   // produced by the conv epilogue: one run per wave row
-}
+    else if (k.M % c.bm != 0 || a->Co != k.CoPad || a->Co % c.bn != 0) p.stats_runs = 0;
+    else p.stats_runs = k.HW / (32 * c.tm);                     // produced by the conv epilogue: one run per wave row
+    if (a->stats_out && p.stats_runs == 0) return EVC_EINVAL;
 
-extern "C" int evc_conv_plan_query(const evc_conv_args* a, evc_conv_plan* out) {
-    if (!out || conv_validate(a) != EVC_OK) return EVC_EINVAL;
-    const TileCfg c = conv_tile_cfg(a);
-    if (evc_conv_kernel_name(a, out->kernel, (int)sizeof(out->kernel)) < 0) return EVC_EINVAL;
-    out->tile_m = c.bm; out->tile_n = c.bn; out->splits = c.splits; out->steps_per_split = c.steps_per_split;
-    out->cut_chunk = c.wide ? c.cut_chunk : 0;
-    out->tail_tiles = c.tail_tiles; out->tail_splits = c.tail_tiles ? c.tail_splits : 1;
-    out->stats_runs = evc_conv_stats_splits(a);
-    out->fused_1x1 = evc_conv_fused_1x1_supported(a);
+    // The fused 1x1 operand exists in the f16x3 row-reuse and wide kernels only (3x3 filters on tiles of whole image rows).
+    // They take one scale per tile; batch-invariant mode has one per sample, so tiles must be whole fractions of a sample.
+    const bool whole = k.HW % c.bm == 0;
+    p.fused_1x1 = a->arith == EVC_ARITH_F16X3 && a->KH == 3 && a->KW == 3 && (c.reuse == 1 || c.wide) && (!a->invariant || whole);
+    p.x2 = a->x2_w_packed != nullptr; k.x2_C0 = k.x2_C1 = k.x2_ld0 = k.x2_ld1 = 0;
+    if (p.x2) {
+        if (!p.fused_1x1) return EVC_EUNSUPPORTED;
+        k.x2_C0 = a->x2_C0; k.x2_C1 = a->x2_C1;
+        k.x2_ld0 = a->x2_ld0 > 0 ? a->x2_ld0 : a->x2_C0;
+        k.x2_ld1 = a->x2_ld1 > 0 ? a->x2_ld1 : (a->x2_C1 > 0 ? a->x2_C1 : k.x2_ld0);
+        if ((long long)k.M * k.x2_ld0 * 4 >= (1LL << 32) || (long long)k.M * k.x2_ld1 * 4 >= (1LL << 32)) return EVC_EUNSUPPORTED;
+    }
+    k.bound_stride = a->invariant ? 1 : 0; k.generic_epi = a->invariant && !whole;
+    if (a->invariant && !whole && (c.reuse || c.wide) && a->in_bound) return EVC_EUNSUPPORTED;
+
+    // the kernel instance, its workgroup and its dynamic LDS
+    p.np = p.nu = 0; p.tm = c.tm; p.tn = c.tn;
+    p.block = dim3(256);
+    if (c.wide) {
+        p.family = FAM_WIDE; p.tm = p.tn = 0; p.nu = a->W == 128 ? 4 : 3;
+        p.lds = (size_t)wide_lds_bytes(a->W, p.x2);
+    } else if (is_split_arith(a->arith)) {
+        p.np = arith_planes(a->arith);
+        p.family = c.reuse ? FAM_RR : p.np == 3 ? FAM_SPLIT3 : FAM_SPLIT2;
+        if (c.reuse) { p.tm = c.bm == 256 ? 4 : 2; p.block = dim3(128 * p.tm); }
+        p.lds = c.reuse ? (size_t)rr_lds_bytes(p.np, c.bm, a->W, c.bn) : (size_t)2 * p.np * (c.bm + c.bn) * 32;
+    } else {
+        p.family = FAM_IGEMM;
+        p.lds = (size_t)2 * (c.bm + c.bn) * KC * sizeof(float);
+    }
+    p.grid = dim3((k.M + c.bm - 1) / c.bm, k.CoPad / c.bn, c.splits);
+    if (c.tail_tiles) p.grid.x = c.tail_first + c.tail_tiles * c.tail_splits;
+    if (c.tail_tiles) p.ws_bytes = (long long)c.tail_splits * c.tail_tiles * c.bm * a->Co * (long long)sizeof(float);
+    else p.ws_bytes = c.splits == 1 ? 0 : (long long)c.splits * k.M * a->Co * (long long)sizeof(float);
     return EVC_OK;
-}
-
-extern "C" long long evc_conv_workspace_bytes(const evc_conv_args* a) {
-    if (conv_validate(a) != EVC_OK) return EVC_EINVAL;
-    const TileCfg c = conv_tile_cfg(a);
-    if (c.tail_tiles) return (long long)c.tail_splits * c.tail_tiles * c.bm * a->Co * (long long)sizeof(float);
-    if (c.splits == 1) return 0;
-    return (long long)c.splits * a->B * a->H * a->W * a->Co * (long long)sizeof(float);
 }
 
 // Kernels that take more than the default 64 KB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised,
@@ -2386,201 +2403,175 @@ static int ensure_dynamic_lds(const void* fn, unsigned long long* done_mask, siz
 #endif
 
 template <int TM, int TN>
-static int launch_mode(int mode, dim3 grid, size_t lds, hipStream_t st, const ConvK& k) {
-#define EVC_CALL(M) hipLaunchKernelGGL((conv_igemm_kernel<TM, TN, M>), grid, dim3(256), lds, st, k)
-    EVC_MODE_SWITCH(mode, EVC_CALL)
+static int launch_mode(const ConvLaunch& p, hipStream_t st) {
+#define EVC_CALL(M) hipLaunchKernelGGL((conv_igemm_kernel<TM, TN, M>), p.grid, p.block, p.lds, st, p.k)
+    EVC_MODE_SWITCH(p.mode, EVC_CALL)
 #undef EVC_CALL
     return EVC_OK;
 }
 
 // bf16x6 off the row-reuse path: the software-pipelined kernel
 template <int TM, int TN>
-static int launch_split3(int mode, dim3 grid, size_t lds, hipStream_t st, const ConvK& k) {
-#define EVC_CALL(M) hipLaunchKernelGGL((conv_split_kernel<TM, TN, M>), grid, dim3(256), lds, st, k)
-    EVC_MODE_SWITCH(mode, EVC_CALL)
+static int launch_split3(const ConvLaunch& p, hipStream_t st) {
+#define EVC_CALL(M) hipLaunchKernelGGL((conv_split_kernel<TM, TN, M>), p.grid, p.block, p.lds, st, p.k)
+    EVC_MODE_SWITCH(p.mode, EVC_CALL)
 #undef EVC_CALL
     return EVC_OK;
 }
 
 // f16x3 off the row-reuse path: the simple-schedule kernel
 template <int TM, int TN>
-static int launch_split2(int mode, dim3 grid, size_t lds, hipStream_t st, const ConvK& k) {
-#define EVC_CALL(M) hipLaunchKernelGGL((conv_splitn_kernel<2, TM, TN, M>), grid, dim3(256), lds, st, k)
-    EVC_MODE_SWITCH(mode, EVC_CALL)
+static int launch_split2(const ConvLaunch& p, hipStream_t st) {
+#define EVC_CALL(M) hipLaunchKernelGGL((conv_splitn_kernel<2, TM, TN, M>), p.grid, p.block, p.lds, st, p.k)
+    EVC_MODE_SWITCH(p.mode, EVC_CALL)
 #undef EVC_CALL
     return EVC_OK;
 }
 
 template <int NP, int WM, int TN, int MODE>
-static int launch_split_rr_one(dim3 grid, size_t lds, hipStream_t st, const ConvK& k) {
+static int launch_split_rr_one(const ConvLaunch& p, hipStream_t st) {
     static unsigned long long attr_done = 0;
-    const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_split_rr_kernel<NP, WM, TN, MODE>), &attr_done, lds);
+    const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_split_rr_kernel<NP, WM, TN, MODE>), &attr_done, p.lds);
     if (rc != EVC_OK) return rc;
-    hipLaunchKernelGGL((conv_split_rr_kernel<NP, WM, TN, MODE>), grid, dim3(128 * WM), lds, st, k);
+    hipLaunchKernelGGL((conv_split_rr_kernel<NP, WM, TN, MODE>), p.grid, p.block, p.lds, st, p.k);
     return EVC_OK;
 }
 template <int NP, int WM, int TN>
-static int launch_split_rr(int mode, dim3 grid, size_t lds, hipStream_t st, const ConvK& k) {
+static int launch_split_rr(const ConvLaunch& p, hipStream_t st) {
     int rc = EVC_OK;
-#define EVC_CALL(M) rc = launch_split_rr_one<NP, WM, TN, M>(grid, lds, st, k)
-    EVC_MODE_SWITCH(mode, EVC_CALL)
+#define EVC_CALL(M) rc = launch_split_rr_one<NP, WM, TN, M>(p, st)
+    EVC_MODE_SWITCH(p.mode, EVC_CALL)
 #undef EVC_CALL
     return rc;
 }
 
 template <int MODE, int NU, bool X2>
-static int launch_wide_one(dim3 grid, size_t lds, hipStream_t st, const ConvK& k) {
+static int launch_wide_one(const ConvLaunch& p, hipStream_t st) {
     static unsigned long long attr_done = 0;
-    const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_wide_kernel<MODE, NU, X2>), &attr_done, lds);
+    const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_wide_kernel<MODE, NU, X2>), &attr_done, p.lds);
     if (rc != EVC_OK) return rc;
-    hipLaunchKernelGGL((conv_wide_kernel<MODE, NU, X2>), grid, dim3(256), lds, st, k);
+    hipLaunchKernelGGL((conv_wide_kernel<MODE, NU, X2>), p.grid, p.block, p.lds, st, p.k);
     return EVC_OK;
 }
 // the wide kernel is instantiated for the two load transforms the score network's 3x3 convolutions use: GroupNorm + SiLU on
 // load (MODE_AFFINE_SILU) and plain (inputs activated by the FIR pass); wide_ok() sends every other mode to the row-reuse kernel
 template <int MODE>
-static int launch_wide_mode(int nu, bool x2, dim3 grid, size_t lds, hipStream_t st, const ConvK& k) {
-    if (nu == 4) return x2 ? launch_wide_one<MODE, 4, true>(grid, lds, st, k) : launch_wide_one<MODE, 4, false>(grid, lds, st, k);
-    return x2 ? launch_wide_one<MODE, 3, true>(grid, lds, st, k) : launch_wide_one<MODE, 3, false>(grid, lds, st, k);
+static int launch_wide_mode(const ConvLaunch& p, hipStream_t st) {
+    if (p.nu == 4) return p.x2 ? launch_wide_one<MODE, 4, true>(p, st) : launch_wide_one<MODE, 4, false>(p, st);
+    return p.x2 ? launch_wide_one<MODE, 3, true>(p, st) : launch_wide_one<MODE, 3, false>(p, st);
 }
-static int launch_wide(int mode, int nu, bool x2, dim3 grid, size_t lds, hipStream_t st, const ConvK& k) {
+static int launch_wide(const ConvLaunch& p, hipStream_t st) {
 #ifdef EVC_DEV_FAST
-    return launch_wide_mode<MODE_AFFINE_SILU>(nu, x2, grid, lds, st, k);
+    return launch_wide_mode<MODE_AFFINE_SILU>(p, st);
 #else
-    if (mode == MODE_AFFINE_SILU) return launch_wide_mode<MODE_AFFINE_SILU>(nu, x2, grid, lds, st, k);
-    if (mode == MODE_PLAIN) return launch_wide_mode<MODE_PLAIN>(nu, x2, grid, lds, st, k);
+    if (p.mode == MODE_AFFINE_SILU) return launch_wide_mode<MODE_AFFINE_SILU>(p, st);
+    if (p.mode == MODE_PLAIN) return launch_wide_mode<MODE_PLAIN>(p, st);
     return EVC_EUNSUPPORTED;
 #endif
 }
 
-#define EVC_TN_SWITCH(tn, CALL) ((tn) == 3 ? CALL(3) : (tn) == 2 ? CALL(2) : CALL(1))
-
-static int conv2d_impl(const evc_conv_args* a, float* ws, void* stream, hipEvent_t ev_start, hipEvent_t ev_conv_end);
-
-extern "C" int evc_conv2d_nhwc_f32(const evc_conv_args* a, float* ws, void* stream) {
-    return conv2d_impl(a, ws, stream, nullptr, nullptr);
+// ---- the ONE place that maps a resolved plan to a kernel instance: its name (as rocprofv3 --kernel-trace prints it, without
+// the namespace) and its launch read the same fields --------------------------------------------------------------------
+static int conv_kernel_name(const ConvLaunch& p, char* buf, int n) {
+    switch (p.family) {
+        case FAM_WIDE: return snprintf(buf, n, "conv_wide_kernel<%d, %d, %s>", p.mode, p.nu, p.x2 ? "true" : "false");
+        case FAM_RR: return snprintf(buf, n, "conv_split_rr_kernel<%d, %d, %d, %d>", p.np, p.tm, p.tn, p.mode);
+        case FAM_SPLIT3: return snprintf(buf, n, "conv_split_kernel<%d, %d, %d>", p.tm, p.tn, p.mode);
+        case FAM_SPLIT2: return snprintf(buf, n, "conv_splitn_kernel<2, %d, %d, %d>", p.tm, p.tn, p.mode);
+        default: return snprintf(buf, n, "conv_igemm_kernel<%d, %d, %d>", p.tm, p.tn, p.mode);
+    }
 }
 
-// Measurement hook (bench.py's roofline leg): the same launch, with `ev_start` recorded on the stream immediately before
-// the convolution kernel and `ev_conv_end` immediately after it -- i.e. BEFORE the split-K combine kernel, so the interval
-// is the convolution kernel's own duration, the number rocprofv3 --kernel-trace reports for it.  Either may be NULL.
-extern "C" int evc_conv2d_nhwc_profiled_f32(const evc_conv_args* a, float* ws, void* stream, void* ev_start,
-                                            void* ev_conv_end) {
-    return conv2d_impl(a, ws, stream, (hipEvent_t)ev_start, (hipEvent_t)ev_conv_end);
+typedef int (*ConvLaunchFn)(const ConvLaunch&, hipStream_t);
+static const ConvLaunchFn LAUNCH_RR[2][2][3] = {       // [NP == 2][WM == 2][3 - TN]
+    {{launch_split_rr<3, 4, 3>, launch_split_rr<3, 4, 2>, launch_split_rr<3, 4, 1>},
+     {launch_split_rr<3, 2, 3>, launch_split_rr<3, 2, 2>, launch_split_rr<3, 2, 1>}},
+    {{launch_split_rr<2, 4, 3>, launch_split_rr<2, 4, 2>, launch_split_rr<2, 4, 1>},
+     {launch_split_rr<2, 2, 3>, launch_split_rr<2, 2, 2>, launch_split_rr<2, 2, 1>}}};
+static const ConvLaunchFn LAUNCH_TM_TN[3][2][3] = {    // [FAM_SPLIT3 / FAM_SPLIT2 / FAM_IGEMM][TM == 1][3 - TN]
+    {{launch_split3<2, 3>, launch_split3<2, 2>, launch_split3<2, 1>}, {launch_split3<1, 3>, launch_split3<1, 2>, launch_split3<1, 1>}},
+    {{launch_split2<2, 3>, launch_split2<2, 2>, launch_split2<2, 1>}, {launch_split2<1, 3>, launch_split2<1, 2>, launch_split2<1, 1>}},
+    {{launch_mode<2, 3>, launch_mode<2, 2>, launch_mode<2, 1>}, {launch_mode<1, 3>, launch_mode<1, 2>, launch_mode<1, 1>}}};
+
+static int conv_kernel_launch(const ConvLaunch& p, hipStream_t st) {
+    if (p.family == FAM_WIDE) return launch_wide(p, st);
+    if (p.family == FAM_RR) return LAUNCH_RR[p.np == 2][p.tm == 2][3 - p.tn](p, st);
+    return LAUNCH_TM_TN[p.family][p.tm == 1][3 - p.tn](p, st);
 }
 
-static int conv2d_impl(const evc_conv_args* a, float* ws, void* stream, hipEvent_t ev_start, hipEvent_t ev_conv_end) {
-    int rc = conv_validate(a);
+// ---- queries: each resolves once and reads the plan; what the launch refuses gets its error code (0 from the first two) ----
+extern "C" int evc_conv_fused_1x1_supported(const evc_conv_args* a) {
+    ConvLaunch p;
+    return conv_resolve(a, p) == EVC_OK ? p.fused_1x1 : 0;
+}
+
+extern "C" int evc_conv_stats_splits(const evc_conv_args* a) {
+    ConvLaunch p;
+    return conv_resolve(a, p) == EVC_OK ? p.stats_runs : 0;
+}
+
+extern "C" int evc_conv_choose_splits(const evc_conv_args* a) {
+    ConvLaunch p;
+    const int rc = conv_resolve(a, p);
+    return rc == EVC_OK ? p.cfg.splits : rc;
+}
+
+extern "C" long long evc_conv_workspace_bytes(const evc_conv_args* a) {
+    ConvLaunch p;
+    const int rc = conv_resolve(a, p);
+    return rc == EVC_OK ? p.ws_bytes : rc;
+}
+
+extern "C" int evc_conv_kernel_name(const evc_conv_args* a, char* buf, int n) {
+    ConvLaunch p;
+    const int rc = !buf || n <= 0 ? EVC_EINVAL : conv_resolve(a, p);
+    return rc == EVC_OK ? conv_kernel_name(p, buf, n) : rc;
+}
+
+extern "C" int evc_conv_plan_query(const evc_conv_args* a, evc_conv_plan* out) {
+    ConvLaunch p;
+    const int rc = !out ? EVC_EINVAL : conv_resolve(a, p);
     if (rc != EVC_OK) return rc;
-    int mode;
-    if (a->coef_a) {
-        if (a->act_in == EVC_ACT_SILU) mode = MODE_AFFINE_SILU;
-        else if (a->act_in == EVC_ACT_NONE) mode = MODE_AFFINE;
-        else return EVC_EUNSUPPORTED;
-    } else {
-        mode = a->act_in == EVC_ACT_SILU ? MODE_SILU : a->act_in == EVC_ACT_RELU ? MODE_RELU : MODE_PLAIN;
-        if (a->act_in != EVC_ACT_NONE && a->act_in != EVC_ACT_SILU && a->act_in != EVC_ACT_RELU) return EVC_EINVAL;
-    }
-    ConvK k;
-    k.src0 = a->src0; k.src1 = a->src1 ? a->src1 : a->src0; k.C0 = a->C0; k.C1 = a->C1;
-    k.ld0 = a->ld0 > 0 ? a->ld0 : a->C0; k.ld1 = a->ld1 > 0 ? a->ld1 : (a->C1 > 0 ? a->C1 : k.ld0);
-    k.coef_a = a->coef_a; k.coef_s = a->coef_s;
-    k.w = a->w_packed; k.bias = a->bias; k.res = a->res; k.ld_res = a->ld_res;
-    k.w_hdr = nullptr;
-    k.in_bound = nullptr;
-    if (a->in_bound) {
-        if (a->arith != EVC_ARITH_F16X3) return EVC_EINVAL;        // only the fp16 split scales its input
-        k.in_bound = a->in_bound;
-    }
+    const TileCfg& c = p.cfg;
+    conv_kernel_name(p, out->kernel, (int)sizeof(out->kernel));
+    out->tile_m = c.bm; out->tile_n = c.bn; out->splits = c.splits; out->steps_per_split = c.steps_per_split;
+    out->cut_chunk = c.cut_chunk; out->tail_tiles = c.tail_tiles; out->tail_splits = c.tail_splits;
+    out->stats_runs = p.stats_runs; out->fused_1x1 = p.fused_1x1;
+    return EVC_OK;
+}
+
+// ---- the launch: resolve, fill in the operands, launch the resolved instance, launch the combine(s) ------------------------
+static void conv_operands(const evc_conv_args* a, float* ws, ConvK& k) {
+    k.src0 = a->src0; k.src1 = a->src1 ? a->src1 : a->src0;
+    k.coef_a = a->coef_a; k.coef_s = a->coef_s; k.in_bound = a->in_bound;
+    k.w = a->w_packed; k.w_hdr = nullptr;
     if (a->arith == EVC_ARITH_F16X3) {     // [header][planes]
         k.w_hdr = a->w_packed;
         k.w = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a->w_packed) + F16_HDR_BYTES);
     }
+    k.bias = a->bias; k.res = a->res; k.ld_res = a->ld_res;
     k.out_scale = a->out_scale; k.act_out = a->act_out; k.out = a->out; k.ld_out = a->ld_out;
-    k.B = a->B; k.H = a->H; k.W = a->W; k.Co = a->Co; k.CoPad = evc_conv_co_pad(a->Co);
-    k.KH = a->KH; k.KW = a->KW;
-    k.M = a->B * a->H * a->W; k.HW = a->H * a->W;
-    // 32-bit byte offsets inside the kernel: each source must stay below 4 GiB
-    if ((long long)k.M * k.ld0 * 4 >= (1LL << 32) || (long long)k.M * k.ld1 * 4 >= (1LL << 32)) return EVC_EUNSUPPORTED;
-    if (a->KH * a->KW > 32) return EVC_EUNSUPPORTED;   // tap-valid bit mask is 32 bits wide
-    k.nchunk = (a->C0 + a->C1) / KC;
-    k.nsteps = a->KH * a->KW * k.nchunk;
-    const TileCfg cfg = conv_tile_cfg(a);
-    k.splits = cfg.splits;
-    k.steps_per_split = cfg.steps_per_split;
     k.ws = ws;
-    if ((k.splits > 1 || cfg.tail_tiles) && !ws) return EVC_EINVAL;
     k.stats = k.splits > 1 ? nullptr : a->stats_out;   // with split-K the combine kernel writes them
-    if (a->stats_out && evc_conv_stats_splits(a) == 0) return EVC_EINVAL;
     k.x2_w = nullptr; k.x2_hdr = nullptr; k.x2_bound = nullptr; k.x2_src0 = k.x2_src1 = nullptr;
-    k.x2_C0 = k.x2_C1 = k.x2_ld0 = k.x2_ld1 = 0;
     if (a->x2_w_packed) {
-        if (a->arith != EVC_ARITH_F16X3 || a->KH != 3 || a->KW != 3 || !(cfg.reuse == 1 || cfg.wide)) return EVC_EUNSUPPORTED;
         k.x2_src0 = a->x2_src0; k.x2_src1 = a->x2_src1 ? a->x2_src1 : a->x2_src0;
-        k.x2_C0 = a->x2_C0; k.x2_C1 = a->x2_C1;
-        k.x2_ld0 = a->x2_ld0 > 0 ? a->x2_ld0 : a->x2_C0;
-        k.x2_ld1 = a->x2_ld1 > 0 ? a->x2_ld1 : (a->x2_C1 > 0 ? a->x2_C1 : k.x2_ld0);
-        if ((long long)k.M * k.x2_ld0 * 4 >= (1LL << 32) || (long long)k.M * k.x2_ld1 * 4 >= (1LL << 32)) return EVC_EUNSUPPORTED;
         k.x2_hdr = a->x2_w_packed;
         k.x2_w = reinterpret_cast<const char*>(a->x2_w_packed) + F16_HDR_BYTES;
         k.x2_bound = a->x2_bound;
     }
-    k.bound_stride = 0; k.generic_epi = 0;
-    if (a->invariant) {
-        const bool whole = k.HW % cfg.bm == 0;                    // tiles are whole fractions of one sample
-        k.bound_stride = 1;
-        k.generic_epi = whole ? 0 : 1;
-        // the row-reuse / wide kernels take one scale per tile
-        if (!whole && (cfg.reuse || cfg.wide) && (a->in_bound || a->x2_w_packed)) return EVC_EUNSUPPORTED;
-    }
-    k.tail_first = 0x7fffffff; k.tail_splits = 1; k.tail_sps = 0; k.tail_rows = 0;
-    k.cut_chunk = cfg.wide ? cfg.cut_chunk : 0;
-    if (cfg.tail_tiles) {
-        k.tail_first = cfg.tail_first; k.tail_splits = cfg.tail_splits; k.tail_sps = cfg.tail_sps;
-        k.tail_rows = cfg.tail_tiles * cfg.bm;
-    }
+}
 
-    dim3 grid((k.M + cfg.bm - 1) / cfg.bm, k.CoPad / cfg.bn, k.splits);
-    if (cfg.tail_tiles) grid.x = cfg.tail_first + cfg.tail_tiles * cfg.tail_splits;
-    hipStream_t st = (hipStream_t)stream;
+// `ev_start` / `ev_conv_end` (either may be NULL): recorded around the convolution kernel alone, BEFORE the combine (evc_hip.h)
+static int conv2d_impl(const evc_conv_args* a, float* ws, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_conv_end) {
+    ConvLaunch p;
+    int rc = conv_resolve(a, p);
+    if (rc != EVC_OK) return rc;
+    if (p.ws_bytes > 0 && !ws) return EVC_EINVAL;
+    const ConvK& k = p.k;
+    conv_operands(a, ws, p.k);
     if (ev_start && hipEventRecord(ev_start, st) != hipSuccess) return EVC_ELAUNCH;
-    if (cfg.wide) {
-        rc = launch_wide(mode, a->W == 128 ? 4 : 3, a->x2_w_packed != nullptr, grid, (size_t)wide_lds_bytes(a->W, a->x2_w_packed != nullptr), st, k);
-    } else if (is_split_arith(a->arith)) {
-        const int np = arith_planes(a->arith);
-        if (cfg.reuse) {
-            const size_t lds_rr = (size_t)rr_lds_bytes(np, cfg.bm, a->W, cfg.bn);
-#define EVC_RR4_3(TN) launch_split_rr<3, 4, TN>(mode, grid, lds_rr, st, k)
-#define EVC_RR2_3(TN) launch_split_rr<3, 2, TN>(mode, grid, lds_rr, st, k)
-#define EVC_RR4_2(TN) launch_split_rr<2, 4, TN>(mode, grid, lds_rr, st, k)
-#define EVC_RR2_2(TN) launch_split_rr<2, 2, TN>(mode, grid, lds_rr, st, k)
-            if (np == 3) rc = cfg.bm == 256 ? EVC_TN_SWITCH(cfg.tn, EVC_RR4_3) : EVC_TN_SWITCH(cfg.tn, EVC_RR2_3);
-            else rc = cfg.bm == 256 ? EVC_TN_SWITCH(cfg.tn, EVC_RR4_2) : EVC_TN_SWITCH(cfg.tn, EVC_RR2_2);
-#undef EVC_RR4_3
-#undef EVC_RR2_3
-#undef EVC_RR4_2
-#undef EVC_RR2_2
-        } else {
-            const size_t lds = (size_t)2 * np * (cfg.bm + cfg.bn) * 32;
-#define EVC_S3_2(TN) launch_split3<2, TN>(mode, grid, lds, st, k)
-#define EVC_S3_1(TN) launch_split3<1, TN>(mode, grid, lds, st, k)
-#define EVC_S2_2(TN) launch_split2<2, TN>(mode, grid, lds, st, k)
-#define EVC_S2_1(TN) launch_split2<1, TN>(mode, grid, lds, st, k)
-            if (np == 3) rc = cfg.tm == 2 ? EVC_TN_SWITCH(cfg.tn, EVC_S3_2) : EVC_TN_SWITCH(cfg.tn, EVC_S3_1);
-            else rc = cfg.tm == 2 ? EVC_TN_SWITCH(cfg.tn, EVC_S2_2) : EVC_TN_SWITCH(cfg.tn, EVC_S2_1);
-#undef EVC_S3_2
-#undef EVC_S3_1
-#undef EVC_S2_2
-#undef EVC_S2_1
-        }
-    } else {
-        const size_t lds = (size_t)2 * (cfg.bm + cfg.bn) * KC * sizeof(float);
-#define EVC_F_2(TN) launch_mode<2, TN>(mode, grid, lds, st, k)
-#define EVC_F_1(TN) launch_mode<1, TN>(mode, grid, lds, st, k)
-        rc = cfg.tm == 2 ? EVC_TN_SWITCH(cfg.tn, EVC_F_2) : EVC_TN_SWITCH(cfg.tn, EVC_F_1);
-#undef EVC_F_2
-#undef EVC_F_1
-    }
+    rc = conv_kernel_launch(p, st);
     if (rc != EVC_OK) return rc;
     if (hipGetLastError() != hipSuccess) return EVC_ELAUNCH;
     if (ev_conv_end && hipEventRecord(ev_conv_end, st) != hipSuccess) return EVC_ELAUNCH;
@@ -2590,8 +2581,8 @@ static int conv2d_impl(const evc_conv_args* a, float* ws, void* stream, hipEvent
                            a->ld_out, a->stats_out);
         if (hipGetLastError() != hipSuccess) return EVC_ELAUNCH;
     }
-    if (cfg.tail_tiles) {       // combine of the tail's rows only
-        const size_t m0 = (size_t)cfg.tail_first * cfg.bm;
+    if (p.cfg.tail_tiles) {       // combine of the tail's rows only
+        const size_t m0 = (size_t)p.cfg.tail_first * p.cfg.bm;
         hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((k.tail_rows + 63) / 64, (k.Co + 63) / 64), dim3(1024), 0, st, ws,
                            k.tail_splits, k.tail_rows, k.Co, a->bias, a->res ? a->res + m0 * a->ld_res : nullptr, a->ld_res,
                            a->out_scale, a->act_out, a->out + m0 * a->ld_out, a->ld_out,
@@ -2599,4 +2590,12 @@ static int conv2d_impl(const evc_conv_args* a, float* ws, void* stream, hipEvent
         if (hipGetLastError() != hipSuccess) return EVC_ELAUNCH;
     }
     return EVC_OK;
+}
+
+extern "C" int evc_conv2d_nhwc_f32(const evc_conv_args* a, float* ws, void* stream) {
+    return conv2d_impl(a, ws, (hipStream_t)stream, nullptr, nullptr);
+}
+
+extern "C" int evc_conv2d_nhwc_profiled_f32(const evc_conv_args* a, float* ws, void* stream, void* ev_start, void* ev_conv_end) {
+    return conv2d_impl(a, ws, (hipStream_t)stream, (hipEvent_t)ev_start, (hipEvent_t)ev_conv_end);
 }

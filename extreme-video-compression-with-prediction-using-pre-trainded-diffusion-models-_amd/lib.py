@@ -724,6 +724,8 @@ CONV_PROFILE = None
 
 def conv_variant(Co):
     """Which conv_igemm_kernel<TN> instantiation serves an output width (mirrors pick_tn in conv_igemm.hip)."""
+    # A restatement of the C function pick_tn(evc_conv_co_pad(Co)) (csrc/conv_igemm.hip), kept only because bench.py reads
+    # ``variant`` from the profile records; the kernel a launch really runs is the record's ``kernel`` (evc_conv_kernel_name).
     cp = (Co + 63) // 64 * 64
     return 3 if cp % 192 == 0 else (2 if cp % 128 == 0 else 1)
 
@@ -760,13 +762,23 @@ def _src(s):
     return ptr(s), s.shape[-1], s.shape[-1], s.shape[:3]
 
 
+def conv_query_args(B, H, W, C0, C1, Co, KH, KW, arith, coef=False, act_in=ACT_NONE, splits=0, x2_ci=0, invariant=False):
+    """``ConvArgs`` for the planner queries below (no launch, works without a GPU): shapes, arithmetic, on-load mode
+    (``coef``: GroupNorm coefficients, ``act_in``), forced splits, channels of a fused 1x1 operand, the batch-invariant flag.
+    The queries read shapes and which pointers are set, never memory, so every pointer is a non-null dummy."""
+    d = c_void_p(16)
+    a = ConvArgs(src0=d, src1=d if C1 else None, C0=C0, C1=C1, coef_a=d if coef else None, coef_s=d if coef else None,
+                 act_in=act_in, w_packed=d, out_scale=1.0, act_out=ACT_NONE, out=d, ld_out=Co, B=B, H=H, W=W, Co=Co, KH=KH,
+                 KW=KW, splits=splits, arith=arith, invariant=int(bool(invariant)))
+    if x2_ci:
+        a.x2_src0, a.x2_C0, a.x2_w_packed, a.x2_bound = d, x2_ci, d, d
+    return a
+
+
 def conv_fused_1x1_supported(B, H, W, Ci, Co, arith, splits=0, invariant=False):
     """Whether a 3x3 convolution of this shape may carry a fused 1x1 operand (``conv2d_nhwc(..., x2=)``): C query.  It
     needs the f16x3 row-reuse kernel, i.e. 128-pixel tiles: very small grids, for which 64-pixel tiles are chosen, do not."""
-    d = c_void_p(16)
-    a = ConvArgs(d, None, Ci, 0, 0, 0, None, None, ACT_NONE, d, None, None, 0, 1.0, ACT_NONE, d, Co, B, H, W, Co, 3, 3, splits,
-                 None, arith, None)
-    a.invariant = int(bool(invariant))
+    a = conv_query_args(B, H, W, Ci, 0, Co, 3, 3, arith, splits=splits, invariant=invariant)
     return bool(hip_lib(require_device=False).evc_conv_fused_1x1_supported(ctypes.byref(a)))
 
 
@@ -774,15 +786,16 @@ def conv_plan(B, H, W, C0, C1, Co, K, arith, coef=False, act_in=ACT_NONE, x2_ci=
     """The whole plan of a convolution without a launch (``evc_conv_plan_query``; works without a GPU): a dict of the kernel
     instance, tile, K split (count, steps per split, cut), K-split tail, fused-moment runs and whether a fused 1x1 operand
     is accepted.  ``coef`` / ``act_in``: the on-load mode (GroupNorm coefficients, activation); ``x2_ci``: channels of a
-    fused 1x1 operand (f16x3 only)."""
-    d = c_void_p(16)      # any non-null pointers: the query reads shapes only
-    a = ConvArgs(d, d if C1 else None, C0, C1, 0, 0, d if coef else None, d if coef else None, act_in, d, None, None, 0, 1.0,
-                 ACT_NONE, d, Co, B, H, W, Co, K, K, splits, None, arith, None)
-    if x2_ci:
-        a.x2_src0, a.x2_C0, a.x2_w_packed, a.x2_bound = d, x2_ci, d, d
-    a.invariant = int(bool(invariant))
+    fused 1x1 operand (f16x3 only).  The C query refuses a fused operand the plan cannot carry, as the launch does; the
+    answer is then the plan of the launch without it (``fused_1x1`` False), which is what the network launches instead."""
+    L = hip_lib(require_device=False)
     out = ConvPlan()
-    _check(hip_lib(require_device=False).evc_conv_plan_query(ctypes.byref(a), ctypes.byref(out)), "evc_conv_plan_query")
+    a = conv_query_args(B, H, W, C0, C1, Co, K, K, arith, coef, act_in, splits, x2_ci, invariant)
+    rc = L.evc_conv_plan_query(ctypes.byref(a), ctypes.byref(out))
+    if rc != 0 and x2_ci:
+        a = conv_query_args(B, H, W, C0, C1, Co, K, K, arith, coef, act_in, splits, 0, invariant)
+        rc = L.evc_conv_plan_query(ctypes.byref(a), ctypes.byref(out))
+    _check(rc, "evc_conv_plan_query")
     return dict(kernel=out.kernel.decode(), tile=(out.tile_m, out.tile_n), splits=out.splits,
                 steps_per_split=out.steps_per_split, cut_chunk=out.cut_chunk, tail_tiles=out.tail_tiles,
                 tail_splits=out.tail_splits, stats_runs=out.stats_runs, fused_1x1=bool(out.fused_1x1))
@@ -861,18 +874,14 @@ def conv2d_nhwc(src0, w_packed, Co, KH, KW, bias=None, src1=None, coef=None, act
 def conv_fused_stats_splits(B, H, W, Ci, Co, KH, KW, splits=0, arith=None):
     """HW/64 or HW/32 when ``conv2d_nhwc(..., want_stats=True)`` gets its moments from the conv epilogue / split-K
     combine for this shape, 0 when it falls back to a separate ``evc_chan_stats_f32`` pass (C query, no launch)."""
-    d = c_void_p(16)   # any non-null pointers: the query validates shapes only
-    a = ConvArgs(d, None, Ci, 0, 0, 0, None, None, ACT_NONE, d, None, None, 0, 1.0, ACT_NONE, d, Co, B, H, W, Co, KH,
-                 KW, splits, None, default_arith() if arith is None else arith, None)
+    a = conv_query_args(B, H, W, Ci, 0, Co, KH, KW, default_arith() if arith is None else arith, splits=splits)
     return hip_lib(require_device=False).evc_conv_stats_splits(ctypes.byref(a))
 
 
 def conv_workspace_bytes(B, H, W, Ci, Co, KH, KW, splits=0, arith=None):
     """Bytes of split-K slabs ``conv2d_nhwc`` takes for this shape: 0 for an unsplit grid, splits x output for split-K,
     tail splits x tail rows when only the last partial round of tiles is split (C query, no launch)."""
-    d = c_void_p(16)
-    a = ConvArgs(d, None, Ci, 0, 0, 0, None, None, ACT_NONE, d, None, None, 0, 1.0, ACT_NONE, d, Co, B, H, W, Co, KH,
-                 KW, splits, None, default_arith() if arith is None else arith, None)
+    a = conv_query_args(B, H, W, Ci, 0, Co, KH, KW, default_arith() if arith is None else arith, splits=splits)
     return hip_lib(require_device=False).evc_conv_workspace_bytes(ctypes.byref(a))
 
 

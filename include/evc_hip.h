@@ -236,7 +236,8 @@ int evc_conv_pack_weights(const float* w, void* packed, int Co, int Ci, int KH, 
 int evc_conv_set_option(const char* name, int value);
 /* Name of the kernel template instance evc_conv2d_nhwc_f32 launches for these arguments, as rocprofv3 --kernel-trace --stats
  * prints it (e.g. "conv_wide_kernel<2, 4, false>"): lets a profile be matched to launches without mirroring the dispatch.
- * Returns the string length (truncated to n - 1) or EVC_EINVAL. */
+ * Returns the string length (truncated to n - 1), or the error code of the launch for arguments it refuses (see
+ * evc_conv_plan_query). */
 int evc_conv_kernel_name(const evc_conv_args* a, char* buf, int n);
 int evc_conv_choose_splits(const evc_conv_args* a);
 int evc_conv_fused_1x1_supported(const evc_conv_args* a);   /* 1: these arguments may carry the fused 1x1 operand */
@@ -268,7 +269,13 @@ int evc_invariant_plan_revision(void);
 /* The whole plan of a convolution, without a launch: the kernel instance (as evc_conv_kernel_name), the pixel x channel
  * tile, the K split (count, K-steps per split, first chunk of the second piece of an unequal 2-way cut or 0), the K-split
  * tail (pixel tiles, ways; 0 / 1 = none), the fused-moment runs per image (evc_conv_stats_splits) and whether a fused 1x1
- * operand is accepted. */
+ * operand is accepted.
+ * The launch and every query (this one, evc_conv_kernel_name, evc_conv_choose_splits, evc_conv_workspace_bytes,
+ * evc_conv_stats_splits, evc_conv_fused_1x1_supported) read one resolved plan, so no query describes a launch that cannot
+ * happen: for arguments evc_conv2d_nhwc_f32 refuses, the first four return the launch's error code and the last two return 0.
+ * Those are: GroupNorm coefficients with an on-load activation other than none / SiLU (EVC_EUNSUPPORTED), an unknown
+ * activation code (EVC_EINVAL), in_bound off EVC_ARITH_F16X3 (EVC_EINVAL), more than 32 filter taps, a source beyond 4 GiB, a
+ * fused 1x1 operand where fused_1x1 is 0, and batch-invariant mode's one-scale-per-tile refusal (all EVC_EUNSUPPORTED). */
 typedef struct {
     char kernel[96];
     int tile_m, tile_n, splits, steps_per_split, cut_chunk, tail_tiles, tail_splits, stats_runs, fused_1x1;

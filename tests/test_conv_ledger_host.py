@@ -62,6 +62,47 @@ def test_named_parity_cases_still_reach_their_kernel(L, module, test):
     assert len(table) == len(launches), (test, len(table), len(launches))     # no stale rows either
 
 
+def _queries(L, a):
+    """Every query entry point's answer for one ``ConvArgs``: (plan_query's code, its plan, {query: answer})."""
+    import ctypes
+    H = L.hip_lib(require_device=False)
+    ref, plan, buf = ctypes.byref(a), L.ConvPlan(), ctypes.create_string_buffer(96)
+    rc = H.evc_conv_plan_query(ref, ctypes.byref(plan))
+    n = H.evc_conv_kernel_name(ref, buf, 96)
+    return rc, plan, dict(name=buf.value.decode() if n >= 0 else n, splits=H.evc_conv_choose_splits(ref),
+                          stats=H.evc_conv_stats_splits(ref), ws=H.evc_conv_workspace_bytes(ref),
+                          fused=H.evc_conv_fused_1x1_supported(ref))
+
+
+def test_single_answer_queries_agree_with_the_plan(L):
+    """Every launch of the product and every ledger case: the five single-answer queries say what evc_conv_plan_query says,
+    and the workspace is the one the plan's fields imply (tail slabs, else split-K slabs, else none)."""
+    cases = list(ledger.product_launches(L)) + ledger.CASES
+    assert len(cases) > 1000
+    for c in cases:
+        a = L.conv_query_args(c.B, c.H, c.W, c.C0, c.C1, c.Co, c.K, c.K, c.arith, coef=bool(c.coef), act_in=c.act,
+                              splits=c.splits, x2_ci=c.x2, invariant=c.invariant)
+        rc, p, q = _queries(L, a)
+        assert rc == 0, c
+        if p.tail_tiles:
+            ws = p.tail_splits * p.tail_tiles * p.tile_m * c.Co * 4
+        else:
+            ws = p.splits * c.B * c.H * c.W * c.Co * 4 if p.splits > 1 else 0
+        assert q == dict(name=p.kernel.decode(), splits=p.splits, stats=p.stats_runs, ws=ws, fused=p.fused_1x1), (c, q)
+
+
+def test_refused_arguments_are_refused_by_every_query(L):
+    """What the launch refuses no query describes: GroupNorm coefficients with ReLU on load (no such load mode), and a fused 1x1
+    operand on a shape whose plan cannot carry it (1 x 8 x 8, 576 -> 576, f16x3: 64-pixel tiles).  The four queries with an
+    error channel return the launch's code (EVC_EUNSUPPORTED), the two yes / no questions say 0."""
+    relu = L.conv_query_args(1, 32, 32, 192, 0, 192, 3, 3, ledger.F16, coef=True, act_in=L.ACT_RELU)
+    assert not L.conv_plan(1, 8, 8, 576, 0, 576, 3, ledger.F16)["fused_1x1"]
+    fused = L.conv_query_args(1, 8, 8, 576, 0, 576, 3, 3, ledger.F16, x2_ci=576)
+    for a in (relu, fused):
+        rc, _, q = _queries(L, a)
+        assert rc == -2 and q == dict(name=-2, splits=-2, stats=0, ws=-2, fused=0), (rc, q)
+
+
 def test_the_promised_row_reuse_cases_are_in_the_ledger():
     """What test_conv3x3_row_reuse_shapes and test_conv_split_k_... describe and the planner no longer gives their shapes: the
     row-reuse kernel at every image width under both split arithmetics, a partial last tile with tiles spanning images at
