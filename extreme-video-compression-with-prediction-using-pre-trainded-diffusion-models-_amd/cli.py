@@ -25,6 +25,9 @@ one more printed line and ``ssim_<idx>.npy`` / ``ssim_frames_<idx>.npy``; a repo
 ``--lpips NET:BACKBONE.pth,LIN.pth`` adds the benchmark's LPIPS (fvd_utils/calculate_lpips.py; lpips.py ``Lpips``, DESIGN.md section
 8e) of every job on the alex, vgg or squeeze backbone: one more printed line and ``lpips_<net>_<idx>.npy`` /
 ``lpips_<net>_frames_<idx>.npy``; ``--lpips-net`` picks the backbone of the ``--policy lpips`` rule (default alex).
+``--fid WEIGHTS.pth`` (pytorch-fid's Inception-v3 file, never fetched) adds the FID and the k-NN precision / recall (evaluation/;
+fid.py, csrc/inception.hip) of every job's 30 decoded frames against the original clip's: one more printed
+line and ``fid_<idx>.npy`` / ``fid_values_<idx>.npy`` / ``pr_values_<idx>.npy``; ``--fid-dims`` picks the Inception block.
 """
 import argparse
 import os
@@ -141,11 +144,30 @@ def build_parser():
                         "NET = alex, vgg or squeeze, then torchvision's checkpoint of the backbone and lpips' weights/v0.1/NET.pth, "
                         "or NET:ONE_SAVED_STATE_DICT.pth; prints one LPIPS(NET): line per job and saves lpips_NET_frames_<idx>.npy "
                         "(jobs, 30) and lpips_NET_<idx>.npy (RD envelope, lower is better)")
+    add_fid_flags(p)
     return p
 
 
 YUV_FLAGS = ("data_yuv", "yuv_geometry", "yuv_upsample", "yuv_out", "yuv_metrics")
-OPT_IN_FLAGS = YUV_FLAGS + ("ssim", "lpips", "lpips_net")       # written to args.yml only when used: a run without them leaves what it always left
+OPT_IN_FLAGS = YUV_FLAGS + ("ssim", "lpips", "lpips_net", "fid", "fid_dims")       # written to args.yml only when used: a run without them leaves what it always left
+
+
+def add_fid_flags(p):
+    """--fid / --fid-dims of city_sender.py and city_receiver.py."""
+    p.add_argument("--fid", type=str, default=None, metavar="WEIGHTS.pth",
+                   help="pytorch-fid's pt_inception-2015-12-05-6726825d.pth (never fetched): also report each job's FID and k-NN "
+                        "precision / recall (k = 3) of the decoded clip's 30 frames against the original's, on the HIP Inception-v3 "
+                        "(evaluation/fid_PR.py, pr.py; fid.py, DESIGN.md section 8f); prints one 'FID: <v> precision: <p> recall: "
+                        "<r>' line per job and saves fid_<idx>.npy (RD envelope, lower is better), fid_values_<idx>.npy (jobs,) and "
+                        "pr_values_<idx>.npy (jobs, 2)")
+    p.add_argument("--fid-dims", type=int, choices=[64, 192, 768, 2048], default=2048,
+                   help="--fid: the Inception block whose features are compared (64, 192, 768: a map's spatial mean; default 2048)")
+
+
+def check_fid_flag(args):
+    """``--fid FILE`` must name a file; said before any GPU work."""
+    if args.fid and not os.path.isfile(args.fid):
+        sys.exit(f"--fid {args.fid}: no such file")
 
 
 def add_yuv_input_flags(p):
@@ -281,6 +303,7 @@ def main(argv=None):
     if args.lpips:
         from .lpips import parse_spec
         parse_spec(args.lpips)           # FileNotFoundError names a missing weight file before any GPU work
+    check_fid_flag(args)
     import yaml
     from . import dist as D
     if D.needs_self_launch(args.gpus):      # parent: starts the ranks before any HIP call, relays their exit status
@@ -332,6 +355,11 @@ def main(argv=None):
     if args.lpips:
         from .lpips import Lpips
         lp = Lpips.from_spec(args.lpips, device=device)
+    inception = None
+    if args.fid:
+        from . import fid as FI
+        inception = FI.InceptionV3.from_file(args.fid, device=device, max_images=30)
+        print(f"Inception-v3 weights of --fid: {args.fid} (features: {args.fid_dims})", flush=True)
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     vf = os.path.join(args.exp, "video_samples", args.video_folder)
@@ -388,6 +416,7 @@ def main(argv=None):
     vids = list(range(args.start_idx + lo, args.start_idx + hi))
 
     gt_feats, fvd_store, yuv_store, ssim_store, ssim_yuv_store, lpips_store = {}, {}, {}, {}, {}, {}
+    fid_gt, fid_store = {}, {}
 
     def job_fvds(jobs):
         """FVD of each decoded clip against its video's original, as city_sender.py:575-577 computes it: calculate_fvd of
@@ -429,6 +458,13 @@ def main(argv=None):
                                  torch.from_numpy(np.ascontiguousarray(gt, dtype=np.float32))).double().cpu().numpy()
             print(f"[rank {rank}] video {vid} q{q} thr {thr:.2f}: LPIPS({lp.net}): {np.mean(lv):.5f}", flush=True)
             lpips_store.setdefault(vid, []).append(lv)
+        if inception is not None:    # FID and precision / recall of the clip's frames against the original's (fid_PR.py, pr.py)
+            if vid not in fid_gt:    # the originals' features: once per video
+                fid_gt[vid] = FI.features(torch.from_numpy(np.ascontiguousarray(gt, dtype=np.float32)), inception, args.fid_dims)
+            fx = FI.features(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)), inception, args.fid_dims)
+            fv, pv, rv = FI.fid_and_pr(fid_gt[vid], fx, k=3)
+            print(f"[rank {rank}] video {vid} q{q} thr {thr:.2f}: FID: {fv:f} precision: {pv:.5f} recall: {rv:.5f}", flush=True)
+            fid_store.setdefault(vid, []).append((fv, pv, rv))
         if args.yuv_metrics:
             from . import video_io as V
             pair = V.yuv_metric_clips(x, gt)
@@ -535,6 +571,11 @@ def main(argv=None):
             np.save(os.path.join(out_root, f"lpips_{lp.net}_{vid}.npy"),
                     rd_envelope(bpps, np.mean(np.asarray(lpips_store[vid]), 1), False))
             np.save(os.path.join(out_root, f"lpips_{lp.net}_frames_{vid}.npy"), np.asarray(lpips_store[vid]))
+        if vid in fid_store:     # --fid: the envelope laid out as psnr_<idx>.npy, lower is better; raw values beside it
+            vals = np.asarray(fid_store[vid])
+            np.save(os.path.join(out_root, f"fid_{vid}.npy"), rd_envelope(bpps, vals[:, 0], False))
+            np.save(os.path.join(out_root, f"fid_values_{vid}.npy"), vals[:, 0])
+            np.save(os.path.join(out_root, f"pr_values_{vid}.npy"), vals[:, 1:])
         if vid in fvd_store:     # reference name fvd_<idx>.npy: RD envelope [bpp; FVD], lower is better; raw values beside it
             np.save(os.path.join(out_root, f"fvd_{vid}.npy"), rd_envelope(bpps, np.asarray(fvd_store[vid]), False))
             np.save(os.path.join(out_root, f"fvd_values_{vid}.npy"), np.asarray(fvd_store[vid]))

@@ -187,6 +187,12 @@ HIP_SYMBOLS = {
     "evc_ssim_workspace_bytes": (c_longlong, [c_int, c_int, c_int]),
     "evc_ssim_planes_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_double, c_void_p, c_void_p,
                                     c_void_p]),
+    "evc_inception_stem_im2col_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
+    "evc_im2col_nhwc_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 11 + [c_void_p]),
+    "evc_pool3x3s1p1_nhwc_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
+    "evc_spatial_mean_nhwc_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p]),
+    "evc_knn_radius_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 3 + [c_void_p]),
+    "evc_manifold_hits_f32": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
 }
 
 RANS_SYMBOLS = {
@@ -537,6 +543,72 @@ def i3d_head(x, T, w, bias, kt):
     return out
 
 
+INCEPTION_RES, INCEPTION_STEM_OUT = 299, 149      # the resize target and the side of Conv2d_1a_3x3's output
+POOL_AVG, POOL_MAX = 0, 1                         # include/evc_hip.h EVC_POOL_*
+
+
+def inception_stem_im2col(x, f_begin, out):
+    """x: (N, 3, H, W) images in [0, 1] -> ``out`` (nf, 149, 149, ld_out): the patch rows of Conv2d_1a_3x3 (3x3, stride 2) over
+    2 * bilinear(x, 299 x 299) - 1 for the images f_begin .. f_begin + nf - 1, (c, ky, kx) order, zeros from column 27."""
+    N, C, H, W = x.shape
+    nf, Ho, Wo, ld = out.shape
+    assert (Ho, Wo) == (INCEPTION_STEM_OUT, INCEPTION_STEM_OUT) and f_begin + nf <= N
+    _check(hip_lib().evc_inception_stem_im2col_f32(fptr(x), fptr(out), N, C, H, W, f_begin, nf, ld, stream_ptr()),
+           "evc_inception_stem_im2col_f32")
+    return out
+
+
+def im2col_nhwc(x, KH, KW, stride=(1, 1), pad=(0, 0), ld_out=None, out=None):
+    """x: (N, H, W, C) -> (N, Ho, Wo, ld_out) patch rows in (ky, kx, c) order, zeros beyond KH*KW*C (include/evc_hip.h)."""
+    N, H, W, C = x.shape
+    Ho, Wo = (H + 2 * pad[0] - KH) // stride[0] + 1, (W + 2 * pad[1] - KW) // stride[1] + 1
+    ld = KH * KW * C if ld_out is None else ld_out
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"im2col_nhwc: a {KH} x {KW} window with padding {tuple(pad)} does not fit {H} x {W}")
+    if out is None:
+        out = torch.empty((N, Ho, Wo, ld), device=x.device, dtype=torch.float32)
+    assert tuple(out.shape) == (N, Ho, Wo, ld)
+    _check(hip_lib().evc_im2col_nhwc_f32(fptr(x), fptr(out), N, H, W, C, KH, KW, stride[0], stride[1], pad[0], pad[1], ld,
+                                         stream_ptr()), "evc_im2col_nhwc_f32")
+    return out
+
+
+def pool3x3s1p1_nhwc(x, mode):
+    """3x3 stride-1 padding-1 pool of (N, H, W, C): POOL_AVG = avg_pool2d(count_include_pad=False), POOL_MAX = max_pool2d."""
+    N, H, W, C = x.shape
+    out = torch.empty_like(x)
+    _check(hip_lib().evc_pool3x3s1p1_nhwc_f32(fptr(x), fptr(out), N, H, W, C, mode, stream_ptr()), "evc_pool3x3s1p1_nhwc_f32")
+    return out
+
+
+def spatial_mean_nhwc(x):
+    """(N, H, W, C) or (N, HW, C) -> (N, C): the mean over the pixels, summation order a function of HW only."""
+    N, C = x.shape[0], x.shape[-1]
+    out = torch.empty((N, C), device=x.device, dtype=torch.float32)
+    _check(hip_lib().evc_spatial_mean_nhwc_f32(fptr(x), fptr(out), N, x.numel() // max(N * C, 1), C, stream_ptr()),
+           "evc_spatial_mean_nhwc_f32")
+    return out
+
+
+def knn_radius(x, k):
+    """x: (n, d) float32 -> (n,) float64: the squared distance of every row to its (k + 1)-th nearest row, itself included."""
+    n, d = x.shape
+    out = torch.empty((n,), device=x.device, dtype=torch.float64)
+    _check(hip_lib().evc_knn_radius_f32(fptr(x), fptr(out, torch.float64), n, d, k, stream_ptr()), "evc_knn_radius_f32")
+    return out
+
+
+def manifold_hits(y, x, radius2):
+    """(m,) int32 flags: row i of y (m, d) lies within squared distance radius2[j] of some row j of x (n, d)."""
+    m, d = y.shape
+    n = x.shape[0]
+    assert x.shape[1] == d and radius2.numel() == n
+    out = torch.empty((m,), device=y.device, dtype=torch.int32)
+    _check(hip_lib().evc_manifold_hits_f32(fptr(y), fptr(x), fptr(radius2, torch.float64), fptr(out, torch.int32), m, n, d,
+                                           stream_ptr()), "evc_manifold_hits_f32")
+    return out
+
+
 class ClockProbe:
     """Shader clock held by the chip while other streams work, measured by a one-wave idle kernel on its own stream
     (``evc_clock_probe``): start it, enqueue the work to be characterised, call ``stop()`` (a stream-ordered write behind that
@@ -799,6 +871,16 @@ def conv_plan(B, H, W, C0, C1, Co, K, arith, coef=False, act_in=ACT_NONE, x2_ci=
     return dict(kernel=out.kernel.decode(), tile=(out.tile_m, out.tile_n), splits=out.splits,
                 steps_per_split=out.steps_per_split, cut_chunk=out.cut_chunk, tail_tiles=out.tail_tiles,
                 tail_splits=out.tail_splits, stats_runs=out.stats_runs, fused_1x1=bool(out.fused_1x1))
+
+
+def conv_accepts(B, H, W, Ci, Co, KH, KW, arith, invariant=False):
+    """Whether ``conv2d_nhwc`` takes a plain KH x KW "same" convolution of this shape: ``evc_conv_plan_query`` and
+    ``evc_conv_workspace_bytes`` both answer without an error code (no launch, works without a GPU).  A caller with another
+    route for the layer (``im2col_nhwc`` + 1x1) asks this first."""
+    lib = hip_lib(require_device=False)
+    a = conv_query_args(B, H, W, Ci, 0, Co, KH, KW, arith, invariant=invariant)
+    return lib.evc_conv_plan_query(ctypes.byref(a), ctypes.byref(ConvPlan())) == 0 and \
+        lib.evc_conv_workspace_bytes(ctypes.byref(a)) >= 0
 
 
 def conv2d_nhwc(src0, w_packed, Co, KH, KW, bias=None, src1=None, coef=None, act_in=ACT_NONE, res=None,

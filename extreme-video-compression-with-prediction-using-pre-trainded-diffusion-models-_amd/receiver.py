@@ -125,6 +125,8 @@ def build_parser():
     p.add_argument("--lpips", type=str, default=None, metavar="NET:BACKBONE.pth,LIN.pth",
                    help="when the original clips are present, also print each job's LPIPS (city_sender.py --lpips: NET = alex, vgg "
                         "or squeeze; frames mapped to [-1, 1], mean of the spatial map) after its PSNR / SSIM")
+    from .cli import add_fid_flags
+    add_fid_flags(p)             # --fid / --fid-dims: with the original clips present, one FID / precision / recall line per job
     return p
 
 
@@ -134,6 +136,7 @@ def main(argv=None):
     if args.lpips:
         from .lpips import parse_spec
         parse_spec(args.lpips)           # FileNotFoundError names a missing weight file before any GPU work
+    cli.check_fid_flag(args)
     from .elic import ElicModel
     from .scorenet import build_score_network
     paths = args.paths or cli.DEFAULT_PATHS
@@ -156,6 +159,10 @@ def main(argv=None):
     if args.lpips:
         from .lpips import Lpips
         lp = Lpips.from_spec(args.lpips, device=device)
+    inception, fid_gt = None, {}
+    if args.fid:
+        from . import fid as FI
+        inception = FI.InceptionV3.from_file(args.fid, device=device, max_images=30)
 
     def model_for(q):
         if q < len(paths) and os.path.exists(paths[q]):
@@ -202,6 +209,11 @@ def main(argv=None):
             line += ", frames: match" if same else ", frames: MISMATCH"
             mismatches += 0 if same else 1
         log(line)
+        if inception is not None and data is not None:       # city_sender.py --fid's line, the originals' features once per video
+            if job["vid"] not in fid_gt:
+                fid_gt[job["vid"]] = FI.features(torch.from_numpy(gt[:len(x)]), inception, args.fid_dims)
+            fx = FI.features(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)), inception, args.fid_dims)
+            log("%s: FID: %f precision: %.5f recall: %.5f" % ((os.path.basename(path),) + FI.fid_and_pr(fid_gt[job["vid"]], fx, k=3)))
     log(f"decoded {len(jobs)} job stream(s) into {args.output_path}")
     if mismatches:
         sys.exit(f"{mismatches} job(s) decoded to other frames than the sender's (frames: MISMATCH)")

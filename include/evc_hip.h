@@ -589,6 +589,51 @@ long long evc_ssim_workspace_bytes(int N, int H, int W);
 int evc_ssim_planes_f32(const float* a, const float* b, int N, int H, int W, const double* taps11, double c1, double c2,
                         double* out, void* ws, void* stream);
 
+/* ---- FID and precision / recall: the Inception-v3 feature network (csrc/inception.hip) ------
+ * The reference's evaluation/ package: pytorch-fid's InceptionV3 (inception.py:84-163 the four blocks, :184-328 the patched
+ * Inception blocks), the features of fid_PR.py:110-167 and the k-NN precision / recall of pr.py.  Activations are NHWC, the
+ * convolutions (BatchNorm folded, ReLU in the epilogue) run on evc_conv2d_nhwc_f32; these are the other pieces.  None of them
+ * allocates; every one returns EVC_EINVAL before any launch for a null pointer, a size <= 0 or a channel count it does not take.
+ *   evc_inception_stem_im2col_f32   images x (N, 3, H, W) NCHW in [0, 1] -> out (nf, 149, 149, ld_out): the patch rows of
+ *                         Conv2d_1a_3x3 (3x3, stride 2, no padding) for the images f_begin .. f_begin + nf - 1, in (c, ky, kx)
+ *                         order, columns 27 .. ld_out-1 zero (ld_out >= 27, a multiple of 4).  The patches are taken over
+ *                         2 * F.interpolate(x, size=(299, 299), mode='bilinear', align_corners=False) - 1 (inception.py:146-153),
+ *                         sampled while gathering: the source position of output index dst is the rational ((2 dst + 1) in -
+ *                         299) / 598, clamped at 0, the upper neighbour clamped to in - 1, evaluated in integers, so both
+ *                         weights of an axis are correctly rounded fp32 values for any in (up-scaling, in = 299, down-scaling
+ *                         without antialiasing).  2x - 1 is applied to the four source pixels, then the two horizontal and
+ *                         the vertical interpolation: at most seven roundings per value, and in = 299 gives 2x - 1 itself.
+ *                         NaN / inf propagate as in torch (a zero weight times inf is NaN).
+ *   evc_im2col_nhwc_f32   x (N, H, W, C) -> out (N, Ho, Wo, ld_out): patch rows in (ky, kx, c) order of a KH x KW window with
+ *                         strides (SH, SW) and zero padding (PH, PW), Ho = (H + 2 PH - KH) / SH + 1; columns KH*KW*C ..
+ *                         ld_out-1 zero.  C % 4 == 0, ld_out % 4 == 0 (16-byte copies: bit exact).  Serves the stride-2 and
+ *                         the unpadded 3x3 convolutions of the network (inception.py:86-98, Mixed_6a, Mixed_7a) and any
+ *                         filter shape evc_conv_plan_query refuses: the convolution is then 1x1 over ld_out channels with
+ *                         weights permuted to (ky, kx, c).
+ *   evc_pool3x3s1p1_nhwc_f32   (N, H, W, C) -> the same shape, window 3x3, stride 1, padding 1, C % 4 == 0.  EVC_POOL_AVG:
+ *                         F.avg_pool2d(count_include_pad=False) of FIDInceptionA / C / E_1 (inception.py:228, 256, 289): the
+ *                         in-image elements added in row-major order in fp32, divided by their count.  EVC_POOL_MAX:
+ *                         F.max_pool2d(x, 3, 1, 1) of FIDInceptionE_2 (:324): the padding does not take part, a NaN is kept.
+ *   evc_spatial_mean_nhwc_f32   x (N, HW, C) -> out (N, C): AdaptiveAvgPool2d((1, 1)) (inception.py:122, fid_PR.py:159-160);
+ *                         C % 4 == 0, N <= 65535.  The order of the additions depends on HW only.
+ *   evc_knn_radius_f32    radius2[i] = the (k + 1)-th smallest squared distance from row i of x (n, d) to the rows of x, row i
+ *                         included: kthvalue(k + 1) of the self-distance matrix (pr.py:45-46), squared.  1 <= k <= 8, n > k,
+ *                         d % 4 == 0.
+ *   evc_manifold_hits_f32   flags[i] = 1 when some row j of x (n, d) has squared distance to row i of y (m, d) at most
+ *                         radius2[j], else 0 (pr.py:47-52: (dist <= NNk).any(dim=1)).  d % 4 == 0.
+ * Both set kernels add the squares of the exact differences (double)a - (double)b in fp64 in an order that depends on d only,
+ * compare squared values (no sqrt enters a decision) and write no n x m matrix. */
+#define EVC_POOL_AVG 0
+#define EVC_POOL_MAX 1
+int evc_inception_stem_im2col_f32(const float* x, float* out, int N, int C, int H, int W, int f_begin, int nf, int ld_out,
+                                  void* stream);
+int evc_im2col_nhwc_f32(const float* x, float* out, int N, int H, int W, int C, int KH, int KW, int SH, int SW, int PH, int PW,
+                        int ld_out, void* stream);
+int evc_pool3x3s1p1_nhwc_f32(const float* x, float* out, int N, int H, int W, int C, int mode, void* stream);
+int evc_spatial_mean_nhwc_f32(const float* x, float* out, int N, int HW, int C, void* stream);
+int evc_knn_radius_f32(const float* x, double* radius2, int n, int d, int k, void* stream);
+int evc_manifold_hits_f32(const float* y, const float* x, const double* radius2, int* flags, int m, int n, int d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
