@@ -17,7 +17,9 @@ job stream per reported job (container format 3; format 4 with ``--batch-invaria
 (``--noise evc``).  ``--gpus N`` (or ``torch.distributed.run``) block-shards the video range over N ranks, one GPU each.
 ``--data_yuv FILE`` reads the clips from a Y4M or raw planar YUV 4:2:0 file instead of ``--data_npy`` (video_io.py: the
 reference's benchmark conventions, converted by the HIP kernels of csrc/yuv.hip), ``--yuv-out`` writes each job's decoded clip
-as ``.y4m`` and ``--yuv-metrics`` adds the PSNR of the reference's codec benchmark.
+as ``.y4m`` and ``--yuv-metrics`` adds the PSNR of the reference's codec benchmark.  ``--yuv-fit crop``
+takes a file of any frame size: every frame is centre-cropped and resized as the reference's read_video does with Pillow, bit
+for bit, on the GPU (csrc/resample.hip); ``--data_frames 'DIR/output_%04d.png'`` reads RGB image files.
 ``--entropy-estimation`` (a reference flag) reports every key frame's rate as the sum of -log2(likelihood), computed on the GPU
 (``ElicModel.estimate``) instead of the length of range-coded strings: same frames, fractional bits.
 ``--ssim`` adds the reference's SSIM (fvd_utils/calculate_ssim.py; ssim.py, csrc/ssim.hip) of every job:
@@ -148,7 +150,7 @@ def build_parser():
     return p
 
 
-YUV_FLAGS = ("data_yuv", "yuv_geometry", "yuv_upsample", "yuv_out", "yuv_metrics")
+YUV_FLAGS = ("data_yuv", "yuv_geometry", "yuv_upsample", "yuv_out", "yuv_metrics", "yuv_fit", "yuv_resize", "data_frames")
 OPT_IN_FLAGS = YUV_FLAGS + ("ssim", "lpips", "lpips_net", "fid", "fid_dims")       # written to args.yml only when used: a run without them leaves what it always left
 
 
@@ -173,11 +175,27 @@ def check_fid_flag(args):
 def add_yuv_input_flags(p):
     p.add_argument("--data_yuv", type=str, default=None,
                    help="read the clips from a .y4m or raw planar YUV 4:2:0 file (8 or 10 bits) instead of --data_npy: consecutive "
-                        "30-frame clips are videos 0, 1, ...; the frame size must be config.data.image_size")
+                        "30-frame clips are videos 0, 1, ...; the frame size must be config.data.image_size unless --yuv-fit "
+                        "crop is given")
     p.add_argument("--yuv-geometry", type=str, default=None,
                    help="raw .yuv only: WxH[@fps][:bits], e.g. 128x128@30:8 (default: from a _<W>x<H>_<fps>Hz_<bits>bit_ file name)")
     p.add_argument("--yuv-upsample", choices=["bicubic", "bilinear", "nearest"], default="bicubic",
                    help="chroma up-sampling of --data_yuv (torch semantics, align_corners=False; the reference uses bicubic)")
+    p.add_argument("--yuv-fit", choices=["refuse", "crop"], default="refuse",
+                   help="--data_yuv / --data_frames of another frame size than config.data.image_size: refuse (default) ends the "
+                        "run; crop fits every frame as the reference's read_video does (bench_uvg.py:577-598) -- the 8-bit RGB "
+                        "frame is centre-cropped to a square and resized as PIL.Image.resize does, bit for bit, on the GPU "
+                        "(csrc/resample.hip).  A file that already has the size is read as without the flag")
+    p.add_argument("--yuv-resize", choices=["lanczos", "bicubic", "bilinear", "hamming", "box"], default="lanczos",
+                   help="--yuv-fit crop: Pillow's resampling filter (the reference uses lanczos)")
+    p.add_argument("--data_frames", type=str, default=None, metavar="PATTERN",
+                   help="'DIR/output_%%04d.png': read the clips from RGB image files instead of --data_npy / --data_yuv (the reference's process_images): "
+                        "frames 0, 1, ... are opened with Pillow until one is missing, consecutive 30-frame clips are videos "
+                        "0, 1, ...; a frame size other than config.data.image_size takes --yuv-fit")
+
+
+def _given(argv, flag):
+    return any(a == flag or a.startswith(flag + "=") for a in argv)
 
 
 def parse_args(argv=None, parser=None):
@@ -185,23 +203,41 @@ def parse_args(argv=None, parser=None):
     p = parser or build_parser()
     argv = sys.argv[1:] if argv is None else list(argv)
     args = p.parse_args(argv)
-    if args.data_yuv and any(a == "--data_npy" or a.startswith("--data_npy=") for a in argv):
+    if args.data_yuv and _given(argv, "--data_npy"):
         p.error("--data_yuv replaces --data_npy: pass one of them")
+    if args.data_frames and (args.data_yuv or _given(argv, "--data_npy")):
+        p.error("--data_frames replaces --data_npy and --data_yuv: pass one of the three")
     if args.yuv_geometry and not args.data_yuv:
         p.error("--yuv-geometry describes the --data_yuv file: pass --data_yuv")
+    if args.yuv_fit == "crop" and not (args.data_yuv or args.data_frames):
+        p.error("--yuv-fit fits the frames of --data_yuv or --data_frames: pass one of them")
+    if _given(argv, "--yuv-resize") and args.yuv_fit != "crop":
+        p.error("--yuv-resize names the filter of --yuv-fit crop: pass --yuv-fit crop")
     return args
 
 
 def load_yuv_clips(args, image_size, log=print):
-    """The clips of ``--data_yuv`` as the (B, 30, 3, H, W) uint8 array --data_npy would have held, and the file's frame rate."""
+    """The clips of ``--data_yuv`` (or ``--data_frames``) as the (B, 30, 3, H, W) uint8 array --data_npy would have held, and the
+    file's frame rate (30 for image frames)."""
     from . import video_io as V
+    fit = dict(fit="crop", size=image_size, resize=args.yuv_resize) if args.yuv_fit == "crop" else {}
+    if args.data_frames:
+        try:
+            data = V.read_frame_clips(args.data_frames, log=log, **fit)
+        except V.VideoFormatError as e:
+            sys.exit(f"--data_frames: {e}")
+        if data.shape[-2:] != (image_size, image_size):
+            sys.exit(f"--data_frames {args.data_frames}: frames are {data.shape[-1]}x{data.shape[-2]}, the model's "
+                     f"config.data.image_size is {image_size}: pass --yuv-fit crop to centre-crop and resize them")
+        return data, 30
     try:
         v = V.open_video(args.data_yuv, args.yuv_geometry)
-        if (v.height, v.width) != (image_size, image_size):
+        if (v.height, v.width) != (image_size, image_size) and not fit:
             sys.exit(f"--data_yuv {args.data_yuv}: frames are {v.width}x{v.height}, the model's config.data.image_size is "
                      f"{image_size}; resizing is not built (the reference resizes with ffmpeg / PIL, which cannot be reproduced "
-                     f"here): scale the file to {image_size}x{image_size} first")
-        return V.read_clips(v, upsample=args.yuv_upsample, log=log), v.fps
+                     f"here): scale the file to {image_size}x{image_size} first, or pass --yuv-fit crop to centre-crop and "
+                     f"resize every frame as the reference's read_video does")
+        return V.read_clips(v, upsample=args.yuv_upsample, log=log, **fit), v.fps
     except V.VideoFormatError as e:
         sys.exit(f"--data_yuv: {e}")
 
@@ -395,10 +431,10 @@ def main(argv=None):
     models = {q: ElicModel(D.broadcast_state_dict(sd_e.get(q), 0, device, world), device=device) for q in args.q}
 
     yuv_fps = 30
-    if args.data_yuv:
+    if args.data_yuv or args.data_frames:
         data, yuv_fps = load_yuv_clips(args, cfg.data.image_size, log=lambda m: print(f"[rank {rank}] {m}", flush=True))
         if args.end_idx >= len(data):
-            sys.exit(f"--data_yuv {args.data_yuv} holds {len(data)} clip(s) of 30 frames; --end_idx {args.end_idx} is beyond them")
+            sys.exit(f"{'--data_yuv ' + args.data_yuv if args.data_yuv else '--data_frames ' + args.data_frames} holds {len(data)} clip(s) of 30 frames; --end_idx {args.end_idx} is beyond them")
     elif os.path.exists(args.data_npy):
         data = np.load(args.data_npy, mmap_mode="r")
     elif args.synthetic:

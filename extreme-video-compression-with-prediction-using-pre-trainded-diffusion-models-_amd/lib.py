@@ -5,6 +5,7 @@ through the C ABI with raw pointers.  There is NO fallback path -- a missing lib
 device raises ``EvcLibraryError`` so a silent eager/CPU substitute can never pass a GPU test.
 """
 import ctypes
+import math
 import os
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_longlong, c_uint, c_uint8, c_ulonglong, c_void_p
 
@@ -184,6 +185,10 @@ HIP_SYMBOLS = {
     "evc_noise_normal_f32": (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_ulonglong, c_uint, c_int, c_void_p]),
     "evc_yuv420_to_rgb": (c_int, [c_void_p] + [c_longlong] * 6 + [c_int] * 5 + [c_void_p, c_int, c_void_p]),
     "evc_rgb_to_yuv420": (c_int, [c_void_p, c_void_p] + [c_longlong] * 6 + [c_int] * 4 + [c_void_p, c_void_p]),
+    "evc_resample_h_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_longlong, c_longlong, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                  c_void_p]),
+    "evc_resample_v_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_longlong, c_longlong, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                  c_void_p]),
     "evc_ssim_workspace_bytes": (c_longlong, [c_int, c_int, c_int]),
     "evc_ssim_planes_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_double, c_void_p, c_void_p,
                                     c_void_p]),
@@ -1239,6 +1244,114 @@ def rgb_to_yuv420(x, events, bits=8, buf=None, first=0, stride=None, offsets=Non
     _check(hip_lib().evc_rgb_to_yuv420(fptr(x.contiguous()), ptr(buf), buf.numel(), first, stride, off[0], off[1], off[2], N, H, W,
                                        bits, ptr(events), stream_ptr()), "evc_rgb_to_yuv420")
     return buf
+
+
+# ---- Pillow's 8-bit resize (include/evc_hip.h evc_resample_h_u8 / evc_resample_v_u8) ----------
+def _sinc(v):
+    return 1.0 if v == 0.0 else math.sin(math.pi * v) / (math.pi * v)
+
+
+def _bicubic_filter(x, a=-0.5):
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    return (((x - 5) * x + 8) * x - 4) * a if x < 2.0 else 0.0
+
+
+def _hamming_filter(x):
+    x = abs(x)
+    if x == 0.0:
+        return 1.0
+    return math.sin(math.pi * x) / (math.pi * x) * (0.54 + 0.46 * math.cos(math.pi * x)) if x < 1.0 else 0.0
+
+
+# name -> (filter, support): Pillow's resampling filters
+RESAMPLE_FILTERS = {
+    "lanczos": (lambda x: _sinc(x) * _sinc(x / 3.0) if -3.0 <= x < 3.0 else 0.0, 3.0),
+    "bicubic": (_bicubic_filter, 2.0),
+    "bilinear": (lambda x: 1.0 - abs(x) if abs(x) < 1.0 else 0.0, 1.0),
+    "hamming": (_hamming_filter, 1.0),
+    "box": (lambda x: 1.0 if -0.5 < x <= 0.5 else 0.0, 0.5),
+}
+RESAMPLE_PRECISION = 22          # 32 - 8 - 2 bits of coefficient
+
+
+def resample_tables(n_in, n_out, filter="lanczos"):
+    """The tables of one axis of Pillow's 8-bit resize from ``n_in`` to ``n_out`` samples -> (bounds (n_out, 2) int32: first
+    source index and tap count, coeffs (n_out, ksize) int32: the taps in units of 2^-22, zero past the count, ksize).  Every
+    step is in Python floats in Pillow's order of operations.  ``filter``: a name of
+    ``RESAMPLE_FILTERS`` or a (function, support) pair.  Refuses (ValueError) a table with which an output's sum of products
+    with 8-bit samples could leave int32, the width the kernels accumulate in."""
+    fn, fsupport = RESAMPLE_FILTERS[filter] if isinstance(filter, str) else filter
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"resample_tables: sizes must be positive, got {n_in} -> {n_out}")
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = fsupport * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    bounds = np.zeros((n_out, 2), dtype=np.int32)
+    coeffs = np.zeros((n_out, ksize), dtype=np.int64)
+    one = float(1 << RESAMPLE_PRECISION)
+    for xx in range(n_out):
+        c = (xx + 0.5) * scale
+        xmin = max(int(c - support + 0.5), 0)
+        n = min(int(c + support + 0.5), n_in) - xmin
+        w = [fn((x + xmin - c + 0.5) / fs) for x in range(n)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        bounds[xx] = (xmin, n)
+        for x, v in enumerate(w):
+            if ww != 0.0:
+                v /= ww
+            coeffs[xx, x] = int(v * one + 0.5) if v >= 0 else int(v * one - 0.5)
+    worst = 255 * int(np.abs(coeffs).sum(1).max()) + (1 << (RESAMPLE_PRECISION - 1))
+    if worst > 2 ** 31 - 1:
+        raise ValueError(f"resample_tables: with this filter a sum of {n_in} -> {n_out} can reach {worst}, beyond int32: refused")
+    return bounds, coeffs.astype(np.int32), ksize
+
+
+_resample_tables = {}      # (n_in, n_out, filter, device) -> (bounds, coeffs, ksize), the arrays on the device
+
+
+def _resample_device_tables(n_in, n_out, filter, device):
+    key = (n_in, n_out, filter, str(device))
+    if key not in _resample_tables:
+        b, k, ksize = resample_tables(n_in, n_out, filter)
+        _resample_tables[key] = (torch.from_numpy(b).to(device), torch.from_numpy(k).to(device), ksize)
+    return _resample_tables[key]
+
+
+def resample_u8(x, out_h, out_w, filter="lanczos", box=None):
+    """PIL.Image.resize((out_w, out_h), filter) of every frame of x, (N, 3, H, W) uint8 on the device -> (N, 3, out_h, out_w)
+    uint8, bit for bit (8 bits per channel: integer arithmetic).  ``box`` = (r0, c0, h, w): the part of
+    each frame that is the image (default: all of it); the passes read it where it lies.  The horizontal pass runs first, the
+    vertical pass on its uint8 result; a pass whose size does not change is skipped, and with both skipped the result is a
+    copy of the box.  ``filter``: a name of ``RESAMPLE_FILTERS``; tables are cached per (size in, size out, filter)."""
+    assert x.dtype == torch.uint8 and x.dim() == 4 and x.is_cuda and x.is_contiguous(), "device-contiguous (N, C, H, W) uint8 required"
+    if filter not in RESAMPLE_FILTERS:
+        raise ValueError(f"resample_u8: filter {filter!r} is not one of {', '.join(RESAMPLE_FILTERS)}")
+    N, C, H, W = x.shape
+    r0, c0, h, w = (0, 0, H, W) if box is None else (int(v) for v in box)
+    if not (0 <= r0 and 0 <= c0 and h >= 1 and w >= 1 and r0 + h <= H and c0 + w <= W and out_h >= 1 and out_w >= 1):
+        raise ValueError(f"resample_u8: box {(r0, c0, h, w)} -> {out_h}x{out_w} does not fit {H}x{W} frames")
+    planes = N * C
+    if planes == 0 or (out_w == w and out_h == h):
+        return x[:, :, r0:r0 + h, c0:c0 + w].contiguous()
+    src, rows, row_stride, plane_stride = x.data_ptr() + r0 * W + c0, h, W, H * W
+    if out_w != w:
+        b, k, ksize = _resample_device_tables(w, out_w, filter, x.device)
+        mid = torch.empty((N, C, h, out_w), dtype=torch.uint8, device=x.device)
+        _check(hip_lib().evc_resample_h_u8(c_void_p(src), planes, h, w, plane_stride, row_stride, ptr(b), ptr(k), ksize, out_w,
+                                           ptr(mid), stream_ptr()), "evc_resample_h_u8")
+        if out_h == h:
+            return mid
+        src, row_stride, plane_stride = mid.data_ptr(), out_w, h * out_w
+    b, k, ksize = _resample_device_tables(h, out_h, filter, x.device)
+    out = torch.empty((N, C, out_h, out_w), dtype=torch.uint8, device=x.device)
+    _check(hip_lib().evc_resample_v_u8(c_void_p(src), planes, rows, out_w, plane_stride, row_stride, ptr(b), ptr(k), ksize, out_h,
+                                       ptr(out), stream_ptr()), "evc_resample_v_u8")
+    return out
 
 
 def gate_residual(a, b, x, out=None):

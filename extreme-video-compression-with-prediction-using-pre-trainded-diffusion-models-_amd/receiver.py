@@ -116,7 +116,7 @@ def build_parser():
                         "counts states per launch")
     p.add_argument("--data_npy", type=str, default="city_bonn.npy", help="original clips: when present, per-job PSNR is printed")
     from .cli import add_yuv_input_flags
-    add_yuv_input_flags(p)       # --data_yuv: the original clips from a Y4M / raw 4:2:0 file instead (city_sender.py's flags)
+    add_yuv_input_flags(p)       # --data_yuv / --data_frames: the original clips from a video file or image frames instead (city_sender.py's flags)
     p.add_argument("--yuv", action="store_true",
                    help="also write decoded_v<vid>_q<q>_thr<thr>.y4m (8-bit 4:2:0, full-range BT.709) beside each .npy")
     p.add_argument("--fps", type=str, default="30", help="--yuv: frame rate of the written files (30, 29.97 or 30000/1001)")
@@ -178,7 +178,7 @@ def main(argv=None):
     if args.share_generations:
         log(f"shared generations: {stats.get('samples', 0)} sample-rounds generated for {stats.get('job_rounds', 0)} job-rounds "
             f"served, {stats.get('key_frames_decoded', 0)} key frames decoded")
-    if args.data_yuv:
+    if args.data_yuv or args.data_frames:
         data, _ = cli.load_yuv_clips(args, cfg.data.image_size, log=log)
     else:
         data = np.load(args.data_npy, mmap_mode="r") if os.path.exists(args.data_npy) else None

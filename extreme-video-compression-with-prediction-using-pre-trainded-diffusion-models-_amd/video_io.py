@@ -248,12 +248,50 @@ def _device(device):
     return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
 
 
-def read_clips(path, frames=30, geometry=None, upsample="bicubic", device=None, log=print):
+FIT_GROUP_BYTES = 1 << 28       # device bytes of full-size RGB held at a time while a clip is fitted
+
+
+def center_box(H, W):
+    """The reference's center_crop (bench_uvg.py:577-582) as (r0, c0, h, w): rows H//2 - m//2 .. H//2 + m//2 and columns
+    W//2 - m//2 .. W//2 + m//2 with m = min(H, W), so an odd m gives a square of side m - 1."""
+    m = min(H, W)
+    return H // 2 - m // 2, W // 2 - m // 2, 2 * (m // 2), 2 * (m // 2)
+
+
+def _check_fit(fit, size, resize):
+    from . import lib as L
+    if fit not in (None, "crop"):
+        raise ValueError(f"fit must be None or 'crop', got {fit!r}")
+    if fit and (size is None or size < 1):
+        raise ValueError("fit='crop' needs the size to fit to")
+    if resize not in L.RESAMPLE_FILTERS:
+        raise ValueError(f"resize filter {resize!r} is not one of {', '.join(L.RESAMPLE_FILTERS)}")
+
+
+def fit_frames_u8(x, size, resize="lanczos"):
+    """x: (N, 3, H, W) uint8 on the device -> (N, 3, size, size): the reference's read_video (bench_uvg.py:588-598) -- centre
+    crop, then Pillow's 8-bit resize with ``resize`` (lib.resample_u8: bit for bit)."""
+    from . import lib as L
+    return L.resample_u8(x, size, size, resize, box=center_box(x.shape[2], x.shape[3]))
+
+
+def fit_line(what, H, W, size, resize):
+    r0, c0, h, w = center_box(H, W)
+    return f"{what}: {W}x{H} frames, centre crop {w}x{h} at column {c0}, row {r0}, resized to {size}x{size} ({resize}, 8-bit, as Pillow)"
+
+
+def read_clips(path, frames=30, geometry=None, upsample="bicubic", device=None, log=print, fit=None, size=None, resize="lanczos"):
     """-> (B, frames, 3, H, W) uint8 RGB, the array ``--data_npy`` would have held: consecutive ``frames``-frame clips of the
     file are videos 0, 1, ...; a trailing partial clip is dropped (one line through ``log``).  Each clip is uploaded as it lies
-    in the file and converted by one launch (evc_yuv420_to_rgb, uint8 form)."""
+    in the file and converted by one launch (evc_yuv420_to_rgb, uint8 form).
+
+    ``fit="crop"``: frames of another size than ``size`` x ``size`` are centre-cropped and resized to it on the device
+    (``fit_frames_u8``, one more line through ``log``) after the same conversion, a group of frames at a time, and only the
+    result comes back: (B, frames, 3, size, size) whatever the source.  A file that already has that size is read as without
+    ``fit``."""
     import torch
     from . import lib as L
+    _check_fit(fit, size, resize)
     v = path if isinstance(path, YuvFile) else open_video(path, geometry)
     slices, dropped = clip_slices(v.n_frames, frames)
     if dropped:
@@ -261,11 +299,74 @@ def read_clips(path, frames=30, geometry=None, upsample="bicubic", device=None, 
     if not slices:
         raise VideoFormatError(f"{v.path}: {v.n_frames} frame(s), fewer than one clip of {frames}")
     dev = _device(device)
-    out = np.empty((len(slices), frames, 3, v.height, v.width), dtype=np.uint8)
+    fitted = fit == "crop" and (v.height, v.width) != (size, size)
+    if fitted:
+        log(fit_line(v.path, v.height, v.width, size, resize))
+    out = np.empty((len(slices), frames, 3) + ((size, size) if fitted else (v.height, v.width)), dtype=np.uint8)
+    group = max(1, FIT_GROUP_BYTES // (3 * v.height * v.width)) if fitted else frames
     for b, (i0, n) in enumerate(slices):
         piece, first, stride = v.chunk(i0, n)
         buf = torch.from_numpy(np.array(piece)).to(dev)
-        out[b] = L.yuv420_to_rgb(buf, n, v.height, v.width, v.bits, upsample, first=first, stride=stride, dtype=torch.uint8).cpu().numpy()
+        for j in range(0, n, group):
+            g = min(group, n - j)
+            rgb = L.yuv420_to_rgb(buf, g, v.height, v.width, v.bits, upsample, first=first + j * stride, stride=stride, dtype=torch.uint8)
+            out[b, j:j + g] = (fit_frames_u8(rgb, size, resize) if fitted else rgb).cpu().numpy()
+    return out
+
+
+def frame_path(pattern, i):
+    try:
+        return pattern % i
+    except (TypeError, ValueError):
+        raise VideoFormatError(f"{pattern!r} is not a frame pattern with one integer field, e.g. 'DIR/output_%04d.png'") from None
+
+
+def read_frame_clips(pattern, frames=30, device=None, log=print, fit=None, size=None, resize="lanczos"):
+    """The reference's own entry (process_images / read_video, bench_uvg.py:588-613): ``pattern % 0``, ``pattern % 1``, ... are
+    opened with Pillow until one is missing -> (B, frames, 3, H, W) uint8 as ``read_clips`` gives it.  Every file must be of
+    mode RGB and of the first one's size.  ``fit="crop"``: frames of another size than ``size`` x ``size`` are uploaded as
+    uint8 and take ``fit_frames_u8``, as in ``read_clips``."""
+    import torch
+    try:
+        from PIL import Image
+    except ImportError:
+        raise VideoFormatError("reading image frames needs Pillow (PIL), which is not installed") from None
+    _check_fit(fit, size, resize)
+    n_files = 0
+    while os.path.isfile(frame_path(pattern, n_files)):
+        n_files += 1
+    if not n_files:
+        raise VideoFormatError(f"{frame_path(pattern, 0)}: no such file")
+    slices, dropped = clip_slices(n_files, frames)
+    if dropped:
+        log(f"{pattern}: {n_files} frames = {len(slices)} clip(s) of {frames}; the last {dropped} frame(s) are dropped")
+    if not slices:
+        raise VideoFormatError(f"{pattern}: {n_files} frame(s), fewer than one clip of {frames}")
+
+    def load(i):
+        with Image.open(frame_path(pattern, i)) as im:
+            if im.mode != "RGB":
+                raise VideoFormatError(f"{frame_path(pattern, i)}: image mode {im.mode}, only RGB is read")
+            return np.asarray(im).transpose(2, 0, 1)
+
+    first = load(0)
+    H, W = first.shape[1:]
+    fitted = fit == "crop" and (H, W) != (size, size)
+    if fitted:
+        log(fit_line(pattern, H, W, size, resize))
+    out = np.empty((len(slices), frames, 3) + ((size, size) if fitted else (H, W)), dtype=np.uint8)
+    group = max(1, FIT_GROUP_BYTES // (3 * H * W))
+    dev = _device(device) if fitted else None
+    for b, (i0, n) in enumerate(slices):
+        for j in range(0, n, group):
+            g = min(group, n - j)
+            x = np.empty((g, 3, H, W), dtype=np.uint8)
+            for t in range(g):
+                f = load(i0 + j + t)
+                if f.shape != (3, H, W):
+                    raise VideoFormatError(f"{frame_path(pattern, i0 + j + t)}: {f.shape[2]}x{f.shape[1]}, the first frame is {W}x{H}")
+                x[t] = f
+            out[b, j:j + g] = fit_frames_u8(torch.from_numpy(x).to(dev), size, resize).cpu().numpy() if fitted else x
     return out
 
 

@@ -573,6 +573,24 @@ int evc_rgb_to_yuv420(const float* rgb, unsigned char* dst, long long dst_bytes,
                       long long off_y, long long off_u, long long off_v, int N, int H, int W, int bits, unsigned* events,
                       void* stream);
 
+/* ---- Pillow's 8-bit resize: fitting a source frame to the model (csrc/resample.hip) ----------
+ * PIL.Image.resize on 8 bits per channel is two integer passes, horizontal then vertical, each rounded to uint8; these are
+ * the passes.  src: `planes` planes of `rows` x `cols` uint8, plane p at src + p * plane_stride, its row r at + r * row_stride
+ * (bytes; row_stride >= cols, no alignment asked), so a crop of a larger image is a pointer offset plus the image's strides.
+ * bounds: n_out x 2 ints (xmin, n), coeffs: n_out x ksize ints, both ON THE DEVICE and the caller's (lib.resample_tables): output
+ * index i along the filtered axis is clamp((2^21 + sum_{x < n} src[xmin + x] * coeffs[i][x]) >> 22, 0, 255), int32 throughout,
+ * arithmetic shift.  The caller guarantees 0 <= xmin, n <= ksize, xmin + n <= the axis' length and that the sum fits int32 (a
+ * window is held inside the axis whatever the table says; no byte outside the planes is read).  dst is packed.  Neither call
+ * allocates; a bad shape (a null pointer, a size <= 0 or above 2^24, row_stride < cols, overlapping planes) returns
+ * EVC_EINVAL (negative) before any launch.  No floats, no atomics: an output byte depends on its own row (column) and the
+ * tables only, not on the other planes of the launch.
+ *   evc_resample_h_u8   along the contiguous axis: dst (planes, rows, n_out)
+ *   evc_resample_v_u8   along the row axis:        dst (planes, n_out, cols) */
+int evc_resample_h_u8(const unsigned char* src, int planes, int rows, int cols, long long plane_stride, long long row_stride,
+                      const int* bounds, const int* coeffs, int ksize, int n_out, unsigned char* dst, void* stream);
+int evc_resample_v_u8(const unsigned char* src, int planes, int rows, int cols, long long plane_stride, long long row_stride,
+                      const int* bounds, const int* coeffs, int ksize, int n_out, unsigned char* dst, void* stream);
+
 /* ---- SSIM: the structural similarity of the reference's metric helpers (csrc/ssim.hip) ------
  * ssim() of fvd_utils/calculate_ssim.py:6-23 for N pairs of planes.  a, b: N contiguous planes of H x W fp32 each, values
  * in [0, 1]; taps11: the 11 window taps in float64 ON THE DEVICE (the host computes cv2.getGaussianKernel(11, 1.5)); c1, c2:
