@@ -20,6 +20,9 @@ reference's benchmark conventions, converted by the HIP kernels of csrc/yuv.hip)
 as ``.y4m`` and ``--yuv-metrics`` adds the PSNR of the reference's codec benchmark.  ``--yuv-fit crop``
 takes a file of any frame size: every frame is centre-cropped and resized as the reference's read_video does with Pillow, bit
 for bit, on the GPU (csrc/resample.hip); ``--data_frames 'DIR/output_%04d.png'`` reads RGB image files.
+``--yuv-fit tile`` codes the whole frame instead: it is cut into overlapping tiles of the model's size on the GPU (csrc/tile.hip),
+every tile's frames are a video of their own (video index = clip * tiles + tile), ``tiles.json`` records the grid and
+``city_stitch.py`` (stitch.py) blends the receiver's decoded tiles back into full frames.
 ``--entropy-estimation`` (a reference flag) reports every key frame's rate as the sum of -log2(likelihood), computed on the GPU
 (``ElicModel.estimate``) instead of the length of range-coded strings: same frames, fractional bits.
 ``--ssim`` adds the reference's SSIM (fvd_utils/calculate_ssim.py; ssim.py, csrc/ssim.hip) of every job:
@@ -150,7 +153,8 @@ def build_parser():
     return p
 
 
-YUV_FLAGS = ("data_yuv", "yuv_geometry", "yuv_upsample", "yuv_out", "yuv_metrics", "yuv_fit", "yuv_resize", "data_frames")
+YUV_FLAGS = ("data_yuv", "yuv_geometry", "yuv_upsample", "yuv_out", "yuv_metrics", "yuv_fit", "yuv_resize", "data_frames",
+             "yuv_tile_overlap")
 OPT_IN_FLAGS = YUV_FLAGS + ("ssim", "lpips", "lpips_net", "fid", "fid_dims")       # written to args.yml only when used: a run without them leaves what it always left
 
 
@@ -176,16 +180,23 @@ def add_yuv_input_flags(p):
     p.add_argument("--data_yuv", type=str, default=None,
                    help="read the clips from a .y4m or raw planar YUV 4:2:0 file (8 or 10 bits) instead of --data_npy: consecutive "
                         "30-frame clips are videos 0, 1, ...; the frame size must be config.data.image_size unless --yuv-fit "
-                        "crop is given")
+                        "crop or tile is given")
     p.add_argument("--yuv-geometry", type=str, default=None,
                    help="raw .yuv only: WxH[@fps][:bits], e.g. 128x128@30:8 (default: from a _<W>x<H>_<fps>Hz_<bits>bit_ file name)")
     p.add_argument("--yuv-upsample", choices=["bicubic", "bilinear", "nearest"], default="bicubic",
                    help="chroma up-sampling of --data_yuv (torch semantics, align_corners=False; the reference uses bicubic)")
-    p.add_argument("--yuv-fit", choices=["refuse", "crop"], default="refuse",
+    p.add_argument("--yuv-fit", choices=["refuse", "crop", "tile"], default="refuse",
                    help="--data_yuv / --data_frames of another frame size than config.data.image_size: refuse (default) ends the "
                         "run; crop fits every frame as the reference's read_video does (bench_uvg.py:577-598) -- the 8-bit RGB "
                         "frame is centre-cropped to a square and resized as PIL.Image.resize does, bit for bit, on the GPU "
-                        "(csrc/resample.hip).  A file that already has the size is read as without the flag")
+                        "(csrc/resample.hip); tile codes the whole frame: it is cut into overlapping image_size x image_size "
+                        "tiles on the GPU (csrc/tile.hip) and every tile's 30 frames are a video of their own, video index = "
+                        "clip * tiles + tile (--start_idx / --end_idx count these); the sender writes tiles.json, and "
+                        "city_stitch.py blends the receiver's decoded tiles back into full frames.  A file that already has "
+                        "the size is read as without the flag")
+    p.add_argument("--yuv-tile-overlap", type=int, default=16, metavar="O",
+                   help="--yuv-fit tile: samples by which neighbouring tiles overlap at least (even, 0 .. image_size / 2; "
+                        "default 16)")
     p.add_argument("--yuv-resize", choices=["lanczos", "bicubic", "bilinear", "hamming", "box"], default="lanczos",
                    help="--yuv-fit crop: Pillow's resampling filter (the reference uses lanczos)")
     p.add_argument("--data_frames", type=str, default=None, metavar="PATTERN",
@@ -209,18 +220,41 @@ def parse_args(argv=None, parser=None):
         p.error("--data_frames replaces --data_npy and --data_yuv: pass one of the three")
     if args.yuv_geometry and not args.data_yuv:
         p.error("--yuv-geometry describes the --data_yuv file: pass --data_yuv")
-    if args.yuv_fit == "crop" and not (args.data_yuv or args.data_frames):
+    if args.yuv_fit in ("crop", "tile") and not (args.data_yuv or args.data_frames):
         p.error("--yuv-fit fits the frames of --data_yuv or --data_frames: pass one of them")
     if _given(argv, "--yuv-resize") and args.yuv_fit != "crop":
         p.error("--yuv-resize names the filter of --yuv-fit crop: pass --yuv-fit crop")
+    if _given(argv, "--yuv-tile-overlap") and args.yuv_fit != "tile":
+        p.error("--yuv-tile-overlap is the overlap of --yuv-fit tile: pass --yuv-fit tile")
+    if args.yuv_fit == "tile":
+        size = _config_image_size(args)
+        if args.yuv_tile_overlap < 0 or args.yuv_tile_overlap % 2 or (size is not None and 2 * args.yuv_tile_overlap > size):
+            p.error(f"--yuv-tile-overlap {args.yuv_tile_overlap} must be even and inside [0, image_size / 2]"
+                    + (f" = [0, {size // 2}]" if size is not None else ""))
     return args
+
+
+def _config_image_size(args):
+    """config.data.image_size of the run these arguments describe, or None when the config cannot be read yet (the run says
+    so itself, later)."""
+    from . import config as C
+    try:
+        return int(C.load_config(args.config, args.config_mod)[0].data.image_size)
+    except Exception:
+        return None
 
 
 def load_yuv_clips(args, image_size, log=print):
     """The clips of ``--data_yuv`` (or ``--data_frames``) as the (B, 30, 3, H, W) uint8 array --data_npy would have held, and the
-    file's frame rate (30 for image frames)."""
+    file's frame rate (30 for image frames).  Under ``--yuv-fit tile`` the videos are the tiles' (video_io.read_clips)."""
     from . import video_io as V
     fit = dict(fit="crop", size=image_size, resize=args.yuv_resize) if args.yuv_fit == "crop" else {}
+    if args.yuv_fit == "tile":
+        try:
+            V.check_overlap(image_size, args.yuv_tile_overlap)
+        except ValueError as e:
+            sys.exit(f"--yuv-tile-overlap: {e}")
+        fit = dict(fit="tile", size=image_size, overlap=args.yuv_tile_overlap)
     if args.data_frames:
         try:
             data = V.read_frame_clips(args.data_frames, log=log, **fit)
@@ -240,6 +274,29 @@ def load_yuv_clips(args, image_size, log=print):
         return V.read_clips(v, upsample=args.yuv_upsample, log=log, **fit), v.fps
     except V.VideoFormatError as e:
         sys.exit(f"--data_yuv: {e}")
+
+
+def source_frame_size(args):
+    """(width, height) of the frames of ``--data_yuv`` / ``--data_frames``, from the file's header or the first image."""
+    from . import video_io as V
+    if args.data_frames:
+        from PIL import Image
+        with Image.open(V.frame_path(args.data_frames, 0)) as im:
+            return im.size
+    v = V.open_video(args.data_yuv, args.yuv_geometry)
+    return v.width, v.height
+
+
+def write_tile_manifests(args, image_size, videos, fps, log=print):
+    """``--yuv-fit tile``: tiles.json into --output_path and --bitstream-dir, what city_stitch.py reads.  videos: the number of
+    tile-videos ``load_yuv_clips`` returned."""
+    from . import video_io as V
+    width, height = source_frame_size(args)
+    m = V.tile_manifest(width, height, image_size, args.yuv_tile_overlap, 0, 30, fps, args.data_yuv or args.data_frames)
+    m["clips"] = videos // (m["ny"] * m["nx"])
+    for d in filter(None, (args.output_path, args.bitstream_dir)):
+        log(f"tile manifest: {V.write_manifest(d, m)}")
+    return m
 
 
 def resolve_fvd(args, log=print):
@@ -435,6 +492,8 @@ def main(argv=None):
         data, yuv_fps = load_yuv_clips(args, cfg.data.image_size, log=lambda m: print(f"[rank {rank}] {m}", flush=True))
         if args.end_idx >= len(data):
             sys.exit(f"{'--data_yuv ' + args.data_yuv if args.data_yuv else '--data_frames ' + args.data_frames} holds {len(data)} clip(s) of 30 frames; --end_idx {args.end_idx} is beyond them")
+        if args.yuv_fit == "tile" and rank == 0:
+            write_tile_manifests(args, cfg.data.image_size, len(data), yuv_fps, log=lambda m: print(f"[rank {rank}] {m}", flush=True))
     elif os.path.exists(args.data_npy):
         data = np.load(args.data_npy, mmap_mode="r")
     elif args.synthetic:

@@ -189,6 +189,9 @@ HIP_SYMBOLS = {
                                   c_void_p]),
     "evc_resample_v_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_longlong, c_longlong, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                   c_void_p]),
+    "evc_tile_grid_check": (c_int, [c_int] * 6 + [c_void_p, c_void_p, c_int]),
+    "evc_tile_gather_u8": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 6),
+    "evc_tile_blend_f32": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 6),
     "evc_ssim_workspace_bytes": (c_longlong, [c_int, c_int, c_int]),
     "evc_ssim_planes_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_double, c_void_p, c_void_p,
                                     c_void_p]),
@@ -1351,6 +1354,53 @@ def resample_u8(x, out_h, out_w, filter="lanczos", box=None):
     out = torch.empty((N, C, out_h, out_w), dtype=torch.uint8, device=x.device)
     _check(hip_lib().evc_resample_v_u8(c_void_p(src), planes, rows, out_w, plane_stride, row_stride, ptr(b), ptr(k), ksize, out_h,
                                        ptr(out), stream_ptr()), "evc_resample_v_u8")
+    return out
+
+
+# ---- whole frames as overlapping tiles (include/evc_hip.h evc_tile_gather_u8 / evc_tile_blend_f32) ----
+_tile_origins = {}         # (oy, ox, device) -> (oy, ox host int32 arrays, the same two on the device)
+
+
+def _tile_grid(N, H, W, S, oy, ox, device, cover, name):
+    """The origin arrays of one grid on the host and on the device (cached per grid), after the library's own check of them
+    against (N, H, W, S) -- made before anything is sized by S."""
+    oy, ox = tuple(int(v) for v in oy), tuple(int(v) for v in ox)
+    hy, hx = np.asarray(oy, dtype=np.int32), np.asarray(ox, dtype=np.int32)
+    _check(hip_lib().evc_tile_grid_check(N, H, W, S, len(oy), len(ox), c_void_p(hy.ctypes.data), c_void_p(hx.ctypes.data), int(cover)),
+           name)
+    key = (oy, ox, str(device))
+    if key not in _tile_origins:
+        _tile_origins[key] = (hy, hx, torch.from_numpy(hy).to(device), torch.from_numpy(hx).to(device))
+    return _tile_origins[key]
+
+
+def tile_gather_u8(x, S, oy, ox):
+    """x: (N, 3, H, W) uint8 on the device -> (ny * nx, N, 3, S, S) uint8: tile ty * nx + tx is rows oy[ty] .. oy[ty] + S - 1 and
+    columns ox[tx] .. ox[tx] + S - 1 of every frame, a copy; past the end of an axis shorter than S its last sample repeats.
+    oy, ox: the origins of ``video_io.tile_grid``, strictly increasing inside [0, max(L - S, 0)] (else ``EvcKernelError``)."""
+    assert x.dtype == torch.uint8 and x.dim() == 4 and x.shape[1] == 3 and x.is_cuda and x.is_contiguous(), \
+        "device-contiguous (N, 3, H, W) uint8 required"
+    N, _, H, W = x.shape
+    hy, hx, dy, dx = _tile_grid(N, H, W, int(S), oy, ox, x.device, False, "evc_tile_gather_u8")
+    out = torch.empty((len(hy) * len(hx), N, 3, S, S), dtype=torch.uint8, device=x.device)
+    _check(hip_lib().evc_tile_gather_u8(ptr(x), N, H, W, S, len(hy), len(hx), c_void_p(hy.ctypes.data), c_void_p(hx.ctypes.data),
+                                        ptr(dy), ptr(dx), ptr(out), stream_ptr()), "evc_tile_gather_u8")
+    return out
+
+
+def tile_blend(tiles, H, W, oy, ox):
+    """tiles: (ny * nx, N, 3, S, S) float32 on the device, laid out as ``tile_gather_u8`` gives them -> (N, 3, H, W) float32:
+    every pixel is the mean of the tiles that cover it under the weights t(ly) * t(lx), t(i) = min(i + 1, S - i), added in
+    ascending tile index in fp32 and divided by their integer sum (bit for bit tests/tile_ref.py).  The origins must cover
+    every pixel (first 0, last max(L - S, 0), steps of at most S), else ``EvcKernelError``."""
+    assert tiles.dtype == torch.float32 and tiles.dim() == 5 and tiles.shape[2] == 3 and tiles.shape[3] == tiles.shape[4] and \
+        tiles.is_cuda and tiles.is_contiguous(), "device-contiguous (tiles, N, 3, S, S) float32 required"
+    T, N, _, S, _ = tiles.shape
+    assert T == len(oy) * len(ox), f"{T} tiles for a {len(oy)} x {len(ox)} grid"
+    hy, hx, dy, dx = _tile_grid(N, int(H), int(W), S, oy, ox, tiles.device, True, "evc_tile_blend_f32")
+    out = torch.empty((N, 3, H, W), dtype=torch.float32, device=tiles.device)
+    _check(hip_lib().evc_tile_blend_f32(ptr(tiles), N, H, W, S, len(hy), len(hx), c_void_p(hy.ctypes.data), c_void_p(hx.ctypes.data),
+                                        ptr(dy), ptr(dx), ptr(out), stream_ptr()), "evc_tile_blend_f32")
     return out
 
 

@@ -6,7 +6,9 @@ The conventions are the reference's codec benchmark's (benchmark/transform.py, b
 
 Parsing, slicing and writing bytes are host code (numpy only).  The colour transforms are the two HIP kernels of csrc/yuv.hip:
 ``read_clips`` / ``write_clip`` / ``yuv_round_trip_u8`` upload a piece of the file as it lies (``FRAME`` markers included) and
-convert it with one launch; there is no CPU substitute for them.
+convert it with one launch; there is no CPU substitute for them.  ``fit="crop"`` fits frames of another size to the model
+(csrc/resample.hip), ``fit="tile"`` cuts them into overlapping tiles of the model's size (csrc/tile.hip; ``tile_grid`` and the
+``tiles.json`` manifest are host code).
 """
 import os
 import re
@@ -258,12 +260,96 @@ def center_box(H, W):
     return H // 2 - m // 2, W // 2 - m // 2, 2 * (m // 2), 2 * (m // 2)
 
 
-def _check_fit(fit, size, resize):
+# ---- whole frames as overlapping tiles (DESIGN.md section 8c "Whole frames") ---------------------------------------
+
+def check_overlap(size, overlap):
+    if overlap < 0 or overlap % 2 or 2 * overlap > size:
+        raise ValueError(f"tile overlap {overlap} must be even and inside [0, {size // 2}] (half the tile size {size})")
+
+
+def tile_axis(L, S, O):
+    """Origins of the S-sample tiles of an axis of L samples that overlap by at least O (0 <= O <= S / 2).  L <= S: one tile at
+    0 (its samples past L repeat the last one and take no part in the blend).  L > S: n = ceil((L - O) / (S - O)) tiles at
+    (k (L - S)) // (n - 1): the first at 0, the last at L - S, steps of 1 .. S - O, every tile inside the axis."""
+    if L < 1 or S < 1 or O < 0 or 2 * O > S:
+        raise ValueError(f"tile_axis: length {L}, tile size {S}, overlap {O}: sizes must be positive and 0 <= overlap <= size / 2")
+    if L <= S:
+        return [0]
+    P = S - O
+    n = -(-(L - O) // P)
+    return [(k * (L - S)) // (n - 1) for k in range(n)]
+
+
+def tile_grid(H, W, S, O):
+    """-> (oy, ox): the row and column origins of the ny x nx tiles of an H x W frame; tile index = ty * nx + tx."""
+    return tile_axis(H, S, O), tile_axis(W, S, O)
+
+
+def tile_line(what, H, W, size, overlap, oy, ox):
+    return (f"{what}: {W}x{H} frames as {len(oy)}x{len(ox)} tiles of {size}x{size} overlapping by at least {overlap}, rows at "
+            f"{list(oy)}, columns at {list(ox)}; video index = clip * {len(oy) * len(ox)} + row * {len(ox)} + column")
+
+
+def tile_frames_u8(x, size, oy, ox):
+    """x: (N, 3, H, W) uint8 on the device -> (ny * nx, N, 3, size, size): lib.tile_gather_u8."""
     from . import lib as L
-    if fit not in (None, "crop"):
-        raise ValueError(f"fit must be None or 'crop', got {fit!r}")
+    return L.tile_gather_u8(x, size, oy, ox)
+
+
+MANIFEST_NAME = "tiles.json"
+MANIFEST_KEYS = ("version", "width", "height", "size", "overlap", "ny", "nx", "oy", "ox", "clips", "frames", "fps", "source")
+
+
+def tile_manifest(width, height, size, overlap, clips, frames, fps, source):
+    """What ``city_stitch.py`` needs to put the tile-videos of a ``--yuv-fit tile`` run back together."""
+    oy, ox = tile_grid(height, width, size, overlap)
+    f = as_fps(fps)
+    return dict(version=1, width=int(width), height=int(height), size=int(size), overlap=int(overlap), ny=len(oy), nx=len(ox),
+                oy=oy, ox=ox, clips=int(clips), frames=int(frames), fps=f"{f.numerator}/{f.denominator}",
+                source=os.path.basename(str(source)))
+
+
+def write_manifest(directory, manifest):
+    import json
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, MANIFEST_NAME)
+    with open(path, "w") as fh:
+        json.dump(manifest, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    return path
+
+
+def read_manifest(path):
+    """tiles.json -> its dict, checked: version 1, every key present, the origins those of ``tile_grid``."""
+    import json
+    try:
+        with open(path) as fh:
+            m = json.load(fh)
+    except (OSError, ValueError) as e:
+        raise VideoFormatError(f"{path}: not a tile manifest ({e})") from None
+    if not isinstance(m, dict) or m.get("version") != 1:
+        raise VideoFormatError(f"{path}: not a version-1 tile manifest")
+    missing = [k for k in MANIFEST_KEYS if k not in m]
+    if missing:
+        raise VideoFormatError(f"{path}: tile manifest without {', '.join(missing)}")
+    try:
+        oy, ox = tile_grid(m["height"], m["width"], m["size"], m["overlap"])
+    except (TypeError, ValueError) as e:
+        raise VideoFormatError(f"{path}: {e}") from None
+    if list(m["oy"]) != oy or list(m["ox"]) != ox or (m["ny"], m["nx"]) != (len(oy), len(ox)):
+        raise VideoFormatError(f"{path}: the origins are not those of a {m['width']}x{m['height']} frame in {m['size']}x{m['size']} "
+                               f"tiles overlapping by {m['overlap']}")
+    return m
+
+
+def _check_fit(fit, size, resize, overlap=None):
+    from . import lib as L
+    if fit not in (None, "crop", "tile"):
+        raise ValueError(f"fit must be None, 'crop' or 'tile', got {fit!r}")
     if fit and (size is None or size < 1):
-        raise ValueError("fit='crop' needs the size to fit to")
+        raise ValueError(f"fit={fit!r} needs the size to fit to")
+    if fit == "tile":
+        check_overlap(size, 16 if overlap is None else overlap)
     if resize not in L.RESAMPLE_FILTERS:
         raise ValueError(f"resize filter {resize!r} is not one of {', '.join(L.RESAMPLE_FILTERS)}")
 
@@ -280,7 +366,8 @@ def fit_line(what, H, W, size, resize):
     return f"{what}: {W}x{H} frames, centre crop {w}x{h} at column {c0}, row {r0}, resized to {size}x{size} ({resize}, 8-bit, as Pillow)"
 
 
-def read_clips(path, frames=30, geometry=None, upsample="bicubic", device=None, log=print, fit=None, size=None, resize="lanczos"):
+def read_clips(path, frames=30, geometry=None, upsample="bicubic", device=None, log=print, fit=None, size=None, resize="lanczos",
+               overlap=16):
     """-> (B, frames, 3, H, W) uint8 RGB, the array ``--data_npy`` would have held: consecutive ``frames``-frame clips of the
     file are videos 0, 1, ...; a trailing partial clip is dropped (one line through ``log``).  Each clip is uploaded as it lies
     in the file and converted by one launch (evc_yuv420_to_rgb, uint8 form).
@@ -288,10 +375,15 @@ def read_clips(path, frames=30, geometry=None, upsample="bicubic", device=None, 
     ``fit="crop"``: frames of another size than ``size`` x ``size`` are centre-cropped and resized to it on the device
     (``fit_frames_u8``, one more line through ``log``) after the same conversion, a group of frames at a time, and only the
     result comes back: (B, frames, 3, size, size) whatever the source.  A file that already has that size is read as without
-    ``fit``."""
+    ``fit``.
+
+    ``fit="tile"``: every frame of another size is cut into the ny x nx overlapping ``size`` x ``size`` tiles of ``tile_grid``
+    (``overlap`` samples at least; lib.tile_gather_u8 after the same conversion, a group of frames at a time, one more line
+    through ``log``) and each tile's frames are a video of their own: (B * ny * nx, frames, 3, size, size), video index =
+    clip * (ny * nx) + tile index."""
     import torch
     from . import lib as L
-    _check_fit(fit, size, resize)
+    _check_fit(fit, size, resize, overlap)
     v = path if isinstance(path, YuvFile) else open_video(path, geometry)
     slices, dropped = clip_slices(v.n_frames, frames)
     if dropped:
@@ -300,17 +392,26 @@ def read_clips(path, frames=30, geometry=None, upsample="bicubic", device=None, 
         raise VideoFormatError(f"{v.path}: {v.n_frames} frame(s), fewer than one clip of {frames}")
     dev = _device(device)
     fitted = fit == "crop" and (v.height, v.width) != (size, size)
+    tiled = fit == "tile" and (v.height, v.width) != (size, size)
     if fitted:
         log(fit_line(v.path, v.height, v.width, size, resize))
-    out = np.empty((len(slices), frames, 3) + ((size, size) if fitted else (v.height, v.width)), dtype=np.uint8)
-    group = max(1, FIT_GROUP_BYTES // (3 * v.height * v.width)) if fitted else frames
+    tiles = 1
+    if tiled:
+        oy, ox = tile_grid(v.height, v.width, size, overlap)
+        tiles = len(oy) * len(ox)
+        log(tile_line(v.path, v.height, v.width, size, overlap, oy, ox))
+    out = np.empty((len(slices) * tiles, frames, 3) + ((size, size) if fitted or tiled else (v.height, v.width)), dtype=np.uint8)
+    group = max(1, FIT_GROUP_BYTES // (3 * v.height * v.width)) if fitted or tiled else frames
     for b, (i0, n) in enumerate(slices):
         piece, first, stride = v.chunk(i0, n)
         buf = torch.from_numpy(np.array(piece)).to(dev)
         for j in range(0, n, group):
             g = min(group, n - j)
             rgb = L.yuv420_to_rgb(buf, g, v.height, v.width, v.bits, upsample, first=first + j * stride, stride=stride, dtype=torch.uint8)
-            out[b, j:j + g] = (fit_frames_u8(rgb, size, resize) if fitted else rgb).cpu().numpy()
+            if tiled:
+                out[b * tiles:(b + 1) * tiles, j:j + g] = tile_frames_u8(rgb, size, oy, ox).cpu().numpy()
+            else:
+                out[b, j:j + g] = (fit_frames_u8(rgb, size, resize) if fitted else rgb).cpu().numpy()
     return out
 
 
@@ -321,17 +422,18 @@ def frame_path(pattern, i):
         raise VideoFormatError(f"{pattern!r} is not a frame pattern with one integer field, e.g. 'DIR/output_%04d.png'") from None
 
 
-def read_frame_clips(pattern, frames=30, device=None, log=print, fit=None, size=None, resize="lanczos"):
+def read_frame_clips(pattern, frames=30, device=None, log=print, fit=None, size=None, resize="lanczos", overlap=16):
     """The reference's own entry (process_images / read_video, bench_uvg.py:588-613): ``pattern % 0``, ``pattern % 1``, ... are
     opened with Pillow until one is missing -> (B, frames, 3, H, W) uint8 as ``read_clips`` gives it.  Every file must be of
     mode RGB and of the first one's size.  ``fit="crop"``: frames of another size than ``size`` x ``size`` are uploaded as
-    uint8 and take ``fit_frames_u8``, as in ``read_clips``."""
+    uint8 and take ``fit_frames_u8``, as in ``read_clips``; ``fit="tile"``: they take ``tile_frames_u8`` and come back as
+    tile-videos, as in ``read_clips``."""
     import torch
     try:
         from PIL import Image
     except ImportError:
         raise VideoFormatError("reading image frames needs Pillow (PIL), which is not installed") from None
-    _check_fit(fit, size, resize)
+    _check_fit(fit, size, resize, overlap)
     n_files = 0
     while os.path.isfile(frame_path(pattern, n_files)):
         n_files += 1
@@ -352,11 +454,17 @@ def read_frame_clips(pattern, frames=30, device=None, log=print, fit=None, size=
     first = load(0)
     H, W = first.shape[1:]
     fitted = fit == "crop" and (H, W) != (size, size)
+    tiled = fit == "tile" and (H, W) != (size, size)
     if fitted:
         log(fit_line(pattern, H, W, size, resize))
-    out = np.empty((len(slices), frames, 3) + ((size, size) if fitted else (H, W)), dtype=np.uint8)
+    tiles = 1
+    if tiled:
+        oy, ox = tile_grid(H, W, size, overlap)
+        tiles = len(oy) * len(ox)
+        log(tile_line(pattern, H, W, size, overlap, oy, ox))
+    out = np.empty((len(slices) * tiles, frames, 3) + ((size, size) if fitted or tiled else (H, W)), dtype=np.uint8)
     group = max(1, FIT_GROUP_BYTES // (3 * H * W))
-    dev = _device(device) if fitted else None
+    dev = _device(device) if fitted or tiled else None
     for b, (i0, n) in enumerate(slices):
         for j in range(0, n, group):
             g = min(group, n - j)
@@ -366,7 +474,10 @@ def read_frame_clips(pattern, frames=30, device=None, log=print, fit=None, size=
                 if f.shape != (3, H, W):
                     raise VideoFormatError(f"{frame_path(pattern, i0 + j + t)}: {f.shape[2]}x{f.shape[1]}, the first frame is {W}x{H}")
                 x[t] = f
-            out[b, j:j + g] = fit_frames_u8(torch.from_numpy(x).to(dev), size, resize).cpu().numpy() if fitted else x
+            if tiled:
+                out[b * tiles:(b + 1) * tiles, j:j + g] = tile_frames_u8(torch.from_numpy(x).to(dev), size, oy, ox).cpu().numpy()
+            else:
+                out[b, j:j + g] = fit_frames_u8(torch.from_numpy(x).to(dev), size, resize).cpu().numpy() if fitted else x
     return out
 
 

@@ -591,6 +591,34 @@ int evc_resample_h_u8(const unsigned char* src, int planes, int rows, int cols, 
 int evc_resample_v_u8(const unsigned char* src, int planes, int rows, int cols, long long plane_stride, long long row_stride,
                       const int* bounds, const int* coeffs, int ksize, int n_out, unsigned char* dst, void* stream);
 
+/* ---- Whole frames: overlapping tiles of the model's size, cut and blended (csrc/tile.hip) ------
+ * A frame larger than the model is coded as ny x nx overlapping S x S tiles, tile t = ty * nx + tx at rows oy[ty] .. oy[ty] + S - 1
+ * and columns ox[tx] .. ox[tx] + S - 1 (video_io.tile_grid computes the origins; the reference has no counterpart).  The origins
+ * are passed twice: oy_host / ox_host (ny / nx ints in host memory) are what is checked, oy / ox are the same values ON THE
+ * DEVICE and the caller's, what the kernels read -- held inside [0, max(L - S, 0)] whatever they say, so no byte outside the
+ * buffers is read.  Neither call allocates; EVC_EINVAL before any launch for a null pointer, a size (N, H, W, S, ny, nx) <= 0
+ * or above 2^24, an origin outside [0, max(L - S, 0)] or origins that are not strictly increasing (so an axis with L <= S has
+ * one tile, at 0).
+ *   evc_tile_grid_check   the checks alone, for a caller that sizes buffers by them.  cover != 0 adds what the blend asks.
+ *   evc_tile_gather_u8    src (N, 3, H, W) uint8 -> dst (ny * nx, N, 3, S, S) uint8, packed:
+ *                         dst[t][n][c][y][x] = src[n][c][min(oy[ty] + y, H - 1)][min(ox[tx] + x, W - 1)] -- a copy; the samples
+ *                         past the end of an axis shorter than S repeat its last one.  16-byte accesses where S % 16 == 0 and
+ *                         the source address allows, bounds-checked bytes elsewhere.
+ *   evc_tile_blend_f32    tiles (ny * nx, N, 3, S, S) fp32 -> out (N, 3, H, W) fp32.  With the integer tent t(i) = min(i + 1,
+ *                         S - i), an output pixel (y, x) visits the tiles that cover it in ascending t, at local (ly, lx) = (y -
+ *                         oy[ty], x - ox[tx]): acc = acc + float(t(ly) * t(lx)) * v in fp32 (product rounded, then the sum; no
+ *                         contraction), den = the integer sum of the weights, out = acc / float(den), IEEE division.  Also
+ *                         EVC_EINVAL unless every pixel is covered: first origin 0, last max(L - S, 0), steps of at most S.
+ *                         The padding samples of an axis shorter than S are never read.  Nothing is clamped: a NaN / inf in a
+ *                         tile reaches exactly the pixels that tile covers.  No atomics; one thread owns 4 adjacent pixels (one
+ *                         16-byte store, W % 4 == 0) or one: a frame's bits depend on its own tiles and the grid only, not on
+ *                         N, its place in the batch or the other frames. */
+int evc_tile_grid_check(int N, int H, int W, int S, int ny, int nx, const int* oy_host, const int* ox_host, int cover);
+int evc_tile_gather_u8(const unsigned char* src, int N, int H, int W, int S, int ny, int nx, const int* oy_host,
+                       const int* ox_host, const int* oy, const int* ox, unsigned char* dst, void* stream);
+int evc_tile_blend_f32(const float* tiles, int N, int H, int W, int S, int ny, int nx, const int* oy_host, const int* ox_host,
+                       const int* oy, const int* ox, float* out, void* stream);
+
 /* ---- SSIM: the structural similarity of the reference's metric helpers (csrc/ssim.hip) ------
  * ssim() of fvd_utils/calculate_ssim.py:6-23 for N pairs of planes.  a, b: N contiguous planes of H x W fp32 each, values
  * in [0, 1]; taps11: the 11 window taps in float64 ON THE DEVICE (the host computes cv2.getGaussianKernel(11, 1.5)); c1, c2:
