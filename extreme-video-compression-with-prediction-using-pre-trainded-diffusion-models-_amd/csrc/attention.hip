@@ -14,6 +14,7 @@
 // One wave = 32 queries; a workgroup of WAVES waves shares each 32-key K/V tile through LDS.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stdio.h>
 #include <type_traits>
 #include "../../include/evc_hip.h"
 
@@ -558,6 +559,7 @@ __global__ __launch_bounds__(256) void attention_kv_planes_kernel(const float* _
 
 template <int D>
 constexpr long long attention_tile_bytes() { return 2LL * 32 * (2 * D + 16) + 2LL * D * 80; }
+constexpr long long attention_tile_bytes_of(int D) { return 2LL * 32 * (2 * D + 16) + 2LL * D * 80; }     // the same, D at run time
 
 // out[b][n][h*D + d] = sum_p w_p * o_p[d] / sum_p w_p * l_p,  w_p = exp(m_p - max_p m_p): the exact online-softmax
 // merge of the key parts (same formula the kernel applies tile by tile).  One thread per (b, n, h, 4 channels).
@@ -1109,24 +1111,90 @@ int attention_allow_lds(const void* fn, size_t lds, unsigned long long& done) {
     return EVC_OK;
 }
 
-// N <= 256 keys, D <= 192: one launch of 4-wave workgroups, one per (sample, head, 32-query block); no workspace
+// bytes of the fp16 kernel's K / V tile images behind the key-part buffers (evc_attention_f16x3_f32 with >= 128 keys and a
+// head width it covers); 0 where no launch can use them
+long long attention_planes_bytes(int B, int heads, int N, int D) {
+    if (N >= 128 && (D == 32 || D == 64 || D == 128 || D == 192))
+        return (long long)B * heads * ((N + 31) / 32) * attention_tile_bytes_of(D);
+    return 0;
+}
+
+// Every decision of one attention launch, resolved once: launch<D>() / launch_short<D>() launch from it and
+// evc_attention_plan_query reports it, so the two cannot drift apart.  `with_bounds`: the caller passed bound words (the
+// fp16-split arithmetic where the plan allows it); `have_ws`: the caller passed a workspace.  rc != EVC_OK: the launch refuses.
+enum AttnFamily { ATTN_SHORT_F32, ATTN_SHORT_F16, ATTN_LONG_F32, ATTN_LONG_F16 };
+struct AttnLaunch {
+    int rc;
+    AttnFamily family;
+    int waves, kparts, tiles_per_part;
+    bool pre, merge;               // K / V tile images written by attention_kv_planes_kernel; attention_merge_kernel runs
+    size_t lds;                    // dynamic LDS of the attention kernel
+    long long parts_bytes;         // key-part buffers at the head of the workspace = offset of the K / V tile images
+    long long ws_bytes;            // what evc_attention_[invariant_]workspace_bytes reports for the shape
+};
+
+AttnLaunch attention_resolve(int B, int heads, int N, int D, bool with_bounds, bool ws, bool inv) {
+    AttnLaunch r = {};
+    r.rc = EVC_OK;
+    if (D != 32 && D != 64 && D != 128 && D != 192 && D != 256) { r.rc = EVC_EUNSUPPORTED; return r; }
+    r.parts_bytes = attention_parts_bytes(B, heads, N, D, inv);
+    r.ws_bytes = r.parts_bytes + attention_planes_bytes(B, heads, N, D);
+    const int Bp = inv ? EVC_INVARIANT_REF_BATCH : B;        // the batch the plan is made for
+    // batch-invariant mode: always the with-workspace plan (the entry point guarantees a workspace wherever that plan uses
+    // one) and the default values of the process-wide A/B switches: the plan is a function of (heads, N, D) only
+    const bool have_ws = inv || ws;
+    const int min_keys = inv ? 128 : g_attn_f16_min_keys;
+    const int pre = inv ? 1 : g_attn_pre;
+    // head widths above 192 stay on the f32 kernel: the fp16 kernel keeps Q (both planes) and O in registers, D/2 + D/2 of them
+    const bool f16_ok = D <= 192;
+    // tiny key sets (N < 128: the 8x8 level) stay on the f32 kernel: with two key tiles there is nothing to amortise the
+    // fp16 conversion of K / V over (measured B=9, 8x8: 26 us f32 vs 39 us fp16 split; 16x16: 81 vs 29; 32x32: 260 vs 155)
+    const bool use_f16 = f16_ok && with_bounds && N >= min_keys;
+    if (f16_ok && !inv && g_attn_short && N <= 256) {
+        // N <= 256 keys, D <= 192: one launch of 4-wave workgroups, one per (sample, head, 32-query block); no workspace
+        r.family = use_f16 ? ATTN_SHORT_F16 : ATTN_SHORT_F32;
+        r.waves = 4; r.kparts = 1; r.tiles_per_part = (N + 31) / 32;
+        r.lds = ATTN_SX_FLOATS * sizeof(float) +
+                (use_f16 ? 2 * (size_t)attention_tile_bytes_of(D) : 2 * (size_t)2 * 32 * (D + 4) * sizeof(float));
+        return r;
+    }
+    const AttnPlan pl = (use_f16 && have_ws) ? attention_plan_f16(Bp, heads, N) : attention_plan(Bp, heads, N, have_ws);
+    r.family = use_f16 ? ATTN_LONG_F16 : ATTN_LONG_F32;
+    r.waves = pl.waves; r.kparts = pl.kparts; r.tiles_per_part = pl.tiles_per_part;
+    r.merge = pl.kparts > 1;
+    if (!ws && (pl.kparts > 1 || (use_f16 && pre && pl.waves == 4 && N >= 512 && inv))) { r.rc = EVC_EINVAL; return r; }   // the plan needs a workspace
+    // with a workspace: K / V converted once per launch into tile images (behind the key-part buffers), staged by LDS-DMA
+    // (from 512 keys on: below that the pre-pass launch costs more than the conversions it saves -- B = 9, 256 keys, 3 heads:
+    // 36 us with it, 29 without; 1024 keys, 2 heads: 110 vs 127 -- profiles/r04_attn_kv_planes_ab.log)
+    r.pre = use_f16 && pl.waves == 4 && ws && pre && N >= 512;
+    r.lds = use_f16 ? (size_t)attention_tile_bytes_of(D) * (r.pre ? 2 : 1) : (size_t)2 * 32 * (D + 4) * sizeof(float);
+    return r;
+}
+
+// the instantiation a resolved launch runs, as rocprofv3 --kernel-trace prints it up to spacing
+void attention_kernel_name(const AttnLaunch& r, int D, char* buf, size_t n) {
+    switch (r.family) {
+        case ATTN_SHORT_F32: snprintf(buf, n, "attention_short_kernel<%d>", D); break;
+        case ATTN_SHORT_F16: snprintf(buf, n, "attention_short_f16_kernel<%d>", D); break;
+        case ATTN_LONG_F32: snprintf(buf, n, "attention_kernel<%d,%d>", D, r.waves); break;
+        case ATTN_LONG_F16: snprintf(buf, n, r.pre ? "attention_f16_kernel<%d,%d,pre>" : "attention_f16_kernel<%d,%d>", D, r.waves); break;
+    }
+}
+
 template <int D>
-int launch_short(const float* q, const float* k, const float* v, int ld, float* out, int ld_out, int B, int heads, int N,
-                 float scale, const unsigned* bounds, bool f16, hipStream_t st) {
-    constexpr size_t SX = ATTN_SX_FLOATS * sizeof(float);
+int launch_short(const AttnLaunch& r, const float* q, const float* k, const float* v, int ld, float* out, int ld_out, int B,
+                 int heads, int N, float scale, const unsigned* bounds, hipStream_t st) {
     const dim3 grid((N + 31) / 32, heads, B);
-    if (f16) {
-        const size_t lds = SX + 2 * (size_t)attention_tile_bytes<D>();
+    if (r.family == ATTN_SHORT_F16) {
         static unsigned long long done = 0;
-        const int rc = attention_allow_lds(reinterpret_cast<const void*>(&attention_short_f16_kernel<D>), lds, done);
+        const int rc = attention_allow_lds(reinterpret_cast<const void*>(&attention_short_f16_kernel<D>), r.lds, done);
         if (rc != EVC_OK) return rc;
-        hipLaunchKernelGGL((attention_short_f16_kernel<D>), grid, dim3(256), lds, st, q, k, v, ld, out, ld_out, N, scale, bounds);
+        hipLaunchKernelGGL((attention_short_f16_kernel<D>), grid, dim3(256), r.lds, st, q, k, v, ld, out, ld_out, N, scale, bounds);
     } else {
-        const size_t lds = SX + 2 * (size_t)2 * 32 * (D + 4) * sizeof(float);
         static unsigned long long done = 0;
-        const int rc = attention_allow_lds(reinterpret_cast<const void*>(&attention_short_kernel<D>), lds, done);
+        const int rc = attention_allow_lds(reinterpret_cast<const void*>(&attention_short_kernel<D>), r.lds, done);
         if (rc != EVC_OK) return rc;
-        hipLaunchKernelGGL((attention_short_kernel<D>), grid, dim3(256), lds, st, q, k, v, ld, out, ld_out, N, scale);
+        hipLaunchKernelGGL((attention_short_kernel<D>), grid, dim3(256), r.lds, st, q, k, v, ld, out, ld_out, N, scale);
     }
     return hipGetLastError() == hipSuccess ? EVC_OK : EVC_ELAUNCH;
 }
@@ -1134,71 +1202,49 @@ int launch_short(const float* q, const float* k, const float* v, int ld, float* 
 template <int D>
 int launch(const float* q, const float* k, const float* v, int ld, float* out, int ld_out, int B, int heads, int N,
            float scale, float* ws, const unsigned* bounds, hipStream_t st, bool inv) {
-    const size_t lds = (size_t)2 * 32 * (D + 4) * sizeof(float);
-    const int Bp = inv ? EVC_INVARIANT_REF_BATCH : B;        // the batch the plan is made for
+    const AttnLaunch r = attention_resolve(B, heads, N, D, bounds != nullptr, ws != nullptr, inv);
+    if (r.rc != EVC_OK) return r.rc;
     const int bstride = inv ? 3 : 0;                         // per-sample bound words
-    // batch-invariant mode: always the with-workspace plan (the entry point guarantees a workspace wherever that plan uses
-    // one) and the default values of the process-wide A/B switches: the plan is a function of (heads, N, D) only
-    const bool have_ws = inv || ws != nullptr;
-    const int min_keys = inv ? 128 : g_attn_f16_min_keys;
-    const int pre = inv ? 1 : g_attn_pre;
-    // head widths above 192 stay on the f32 kernel: the fp16 kernel keeps Q (both planes) and O in registers, D/2 + D/2 of them
     constexpr bool F16_OK = D <= 192;
-    const bool use_f16 = F16_OK && bounds && N >= min_keys;
     if constexpr (F16_OK)
-        if (!inv && g_attn_short && N <= 256) return launch_short<D>(q, k, v, ld, out, ld_out, B, heads, N, scale, bounds, use_f16, st);
-    const AttnPlan pl = (use_f16 && have_ws) ? attention_plan_f16(Bp, heads, N) : attention_plan(Bp, heads, N, have_ws);
-    const int waves = pl.waves;
-    if (!ws && (pl.kparts > 1 || (use_f16 && pre && waves == 4 && N >= 512 && inv))) return EVC_EINVAL;   // the plan needs a workspace
+        if (r.family == ATTN_SHORT_F32 || r.family == ATTN_SHORT_F16)
+            return launch_short<D>(r, q, k, v, ld, out, ld_out, B, heads, N, scale, bounds, st);
+    const int waves = r.waves;
     float* part_o = ws;
-    float* part_ml = ws ? ws + (size_t)pl.kparts * B * N * heads * D : nullptr;
-    dim3 grid(((N + 32 * waves - 1) / (32 * waves)) * pl.kparts, heads, B);
-    // tiny key sets (N < 128: the 8x8 level) stay on the f32 kernel: with two key tiles there is nothing to amortise the
-    // fp16 conversion of K / V over (measured B=9, 8x8: 26 us f32 vs 39 us fp16 split; 16x16: 81 vs 29; 32x32: 260 vs 155)
-    if constexpr (F16_OK) if (use_f16) {
-        const size_t lds16 = (size_t)attention_tile_bytes<D>();
-        // with a workspace: K / V converted once per launch into tile images (behind the key-part buffers), staged by LDS-DMA
-        // (from 512 keys on: below that the pre-pass launch costs more than the conversions it saves -- B = 9, 256 keys, 3 heads:
-        // 36 us with it, 29 without; 1024 keys, 2 heads: 110 vs 127 -- profiles/r04_attn_kv_planes_ab.log)
-        if (waves == 4 && ws && pre && N >= 512) {
+    float* part_ml = ws ? ws + (size_t)r.kparts * B * N * heads * D : nullptr;
+    dim3 grid(((N + 32 * waves - 1) / (32 * waves)) * r.kparts, heads, B);
+    if constexpr (F16_OK) if (r.family == ATTN_LONG_F16) {
+        if (r.pre) {
             const int ntiles = (N + 31) / 32;
-            char* planes = reinterpret_cast<char*>(ws) + attention_parts_bytes(B, heads, N, D, inv);
-            hipLaunchKernelGGL((attention_kv_planes_kernel<D>), dim3(ntiles, heads, B), dim3(256), lds16, st, k, v, ld, N, bounds, planes, bstride);
-            if (2 * lds16 > 64 * 1024) {
-                static unsigned long long done = 0;                   // one bit per device id
-                int dev = 0;
-                if (hipGetDevice(&dev) != hipSuccess) return EVC_ELAUNCH;
-                const unsigned long long bit = 1ULL << (dev & 63);
-                if (!(__atomic_load_n(&done, __ATOMIC_ACQUIRE) & bit)) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_kernel<D, 4, true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds16)) != hipSuccess) return EVC_ELAUNCH;
-                    __atomic_fetch_or(&done, bit, __ATOMIC_RELEASE);
-                }
-            }
-            hipLaunchKernelGGL((attention_f16_kernel<D, 4, true>), grid, dim3(256), 2 * lds16, st, q, k, v, ld, out, ld_out, N, scale,
-                               bounds, pl.kparts, pl.tiles_per_part, part_o, part_ml, planes, bstride);
+            char* planes = reinterpret_cast<char*>(ws) + r.parts_bytes;
+            hipLaunchKernelGGL((attention_kv_planes_kernel<D>), dim3(ntiles, heads, B), dim3(256), r.lds / 2, st, k, v, ld, N, bounds, planes, bstride);
+            static unsigned long long done = 0;                   // one bit per device id
+            const int rc = attention_allow_lds(reinterpret_cast<const void*>(&attention_f16_kernel<D, 4, true>), r.lds, done);
+            if (rc != EVC_OK) return rc;
+            hipLaunchKernelGGL((attention_f16_kernel<D, 4, true>), grid, dim3(256), r.lds, st, q, k, v, ld, out, ld_out, N, scale,
+                               bounds, r.kparts, r.tiles_per_part, part_o, part_ml, planes, bstride);
         } else if (waves == 4)
-            hipLaunchKernelGGL((attention_f16_kernel<D, 4>), grid, dim3(256), lds16, st, q, k, v, ld, out, ld_out, N, scale,
-                               bounds, pl.kparts, pl.tiles_per_part, part_o, part_ml, nullptr, bstride);
+            hipLaunchKernelGGL((attention_f16_kernel<D, 4>), grid, dim3(256), r.lds, st, q, k, v, ld, out, ld_out, N, scale,
+                               bounds, r.kparts, r.tiles_per_part, part_o, part_ml, nullptr, bstride);
         else if (waves == 2)
-            hipLaunchKernelGGL((attention_f16_kernel<D, 2>), grid, dim3(128), lds16, st, q, k, v, ld, out, ld_out, N, scale,
-                               bounds, pl.kparts, pl.tiles_per_part, part_o, part_ml, nullptr, bstride);
+            hipLaunchKernelGGL((attention_f16_kernel<D, 2>), grid, dim3(128), r.lds, st, q, k, v, ld, out, ld_out, N, scale,
+                               bounds, r.kparts, r.tiles_per_part, part_o, part_ml, nullptr, bstride);
         else
-            hipLaunchKernelGGL((attention_f16_kernel<D, 1>), grid, dim3(64), lds16, st, q, k, v, ld, out, ld_out, N, scale,
-                               bounds, pl.kparts, pl.tiles_per_part, part_o, part_ml, nullptr, bstride);
+            hipLaunchKernelGGL((attention_f16_kernel<D, 1>), grid, dim3(64), r.lds, st, q, k, v, ld, out, ld_out, N, scale,
+                               bounds, r.kparts, r.tiles_per_part, part_o, part_ml, nullptr, bstride);
     }
-    if (!use_f16) {
-        const int rc = waves == 4 ? launch_f32<D, 4>(grid, lds, st, q, k, v, ld, out, ld_out, N, scale, pl.kparts, pl.tiles_per_part, part_o, part_ml)
-                     : waves == 2 ? launch_f32<D, 2>(grid, lds, st, q, k, v, ld, out, ld_out, N, scale, pl.kparts, pl.tiles_per_part, part_o, part_ml)
-                                  : launch_f32<D, 1>(grid, lds, st, q, k, v, ld, out, ld_out, N, scale, pl.kparts, pl.tiles_per_part, part_o, part_ml);
+    if (r.family == ATTN_LONG_F32) {
+        const int rc = waves == 4 ? launch_f32<D, 4>(grid, r.lds, st, q, k, v, ld, out, ld_out, N, scale, r.kparts, r.tiles_per_part, part_o, part_ml)
+                     : waves == 2 ? launch_f32<D, 2>(grid, r.lds, st, q, k, v, ld, out, ld_out, N, scale, r.kparts, r.tiles_per_part, part_o, part_ml)
+                                  : launch_f32<D, 1>(grid, r.lds, st, q, k, v, ld, out, ld_out, N, scale, r.kparts, r.tiles_per_part, part_o, part_ml);
         if (rc != EVC_OK) return rc;
     }
     if (hipGetLastError() != hipSuccess) return EVC_ELAUNCH;
-    if (pl.kparts > 1) {
+    if (r.merge) {
         const size_t total = (size_t)B * N * heads * (D / 4);
         const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
         hipLaunchKernelGGL(attention_merge_kernel, dim3(blocks), dim3(256), 0, st, part_o, part_ml, out, ld_out, B, heads, N,
-                           D, pl.kparts);
+                           D, r.kparts);
         if (hipGetLastError() != hipSuccess) return EVC_ELAUNCH;
     }
     return EVC_OK;
@@ -1230,11 +1276,8 @@ extern "C" int evc_attention_f32(const float* q, const float* k, const float* v,
 
 static long long attention_ws_bytes(int B, int heads, int N, int D, bool inv) {
     if (B <= 0 || heads <= 0 || N <= 0 || D <= 0) return EVC_EINVAL;
-    long long n = attention_parts_bytes(B, heads, N, D, inv);     // key-part buffers: one size serves both kernels
-    // + the K / V tile images of the fp16 kernel (evc_attention_f16x3_f32 with >= 128 keys and a head width it covers)
-    if (N >= 128 && D <= 192 && (D == 32 || D == 64 || D == 128 || D == 192))
-        n += (long long)B * heads * ((N + 31) / 32) * (2LL * 32 * (2 * D + 16) + 2LL * D * 80);
-    return n;
+    // key-part buffers (one size serves both kernels) + the K / V tile images of the fp16 kernel
+    return attention_parts_bytes(B, heads, N, D, inv) + attention_planes_bytes(B, heads, N, D);
 }
 
 extern "C" long long evc_attention_workspace_bytes(int B, int heads, int N, int D) {
@@ -1277,4 +1320,19 @@ extern "C" int evc_attention_f16x3_f32(const float* q, const float* k, const flo
     if (!bounds) return EVC_EINVAL;
     if (evc_attention_workspace_bytes(B, heads, N, D) > 0 && !ws) return EVC_EINVAL;
     return attention_dispatch(q, k, v, ld_qkv, out, ld_out, B, heads, N, D, scale, ws, bounds, stream);
+}
+
+extern "C" int evc_attention_plan_query(int B, int heads, int N, int D, int with_bounds, int have_ws, int invariant,
+                                        evc_attention_plan* out) {
+    if (!out || B <= 0 || heads <= 0 || N <= 0) return EVC_EINVAL;
+    const AttnLaunch r = attention_resolve(B, heads, N, D, with_bounds != 0, have_ws != 0, invariant != 0);
+    if (r.rc != EVC_OK) return r.rc;
+    // evc_attention_f16x3_f32 and evc_attention_invariant_f32 ask for the workspace before they dispatch
+    if (!have_ws && (with_bounds || invariant) && r.ws_bytes > 0) return EVC_EINVAL;
+    attention_kernel_name(r, D, out->kernel, sizeof(out->kernel));
+    out->waves = r.waves; out->kparts = r.kparts; out->tiles_per_part = r.tiles_per_part;
+    out->kv_planes = r.pre; out->merge = r.merge;
+    out->short_seq = r.family == ATTN_SHORT_F32 || r.family == ATTN_SHORT_F16;
+    out->lds_bytes = (long long)r.lds; out->parts_bytes = r.parts_bytes; out->ws_bytes = r.ws_bytes;
+    return EVC_OK;
 }

@@ -79,6 +79,13 @@ class ConvPlan(ctypes.Structure):
                 ("stats_runs", c_int), ("fused_1x1", c_int)]
 
 
+class AttentionPlan(ctypes.Structure):
+    """Mirror of ``evc_attention_plan`` (include/evc_hip.h): what ``evc_attention_plan_query`` reports."""
+    _fields_ = [("kernel", ctypes.c_char * 64), ("waves", c_int), ("kparts", c_int), ("tiles_per_part", c_int),
+                ("kv_planes", c_int), ("merge", c_int), ("short_seq", c_int),
+                ("lds_bytes", c_longlong), ("parts_bytes", c_longlong), ("ws_bytes", c_longlong)]
+
+
 # name -> (restype, argtypes); exactly the symbols declared in include/evc_hip.h
 HIP_SYMBOLS = {
     "evc_version": (c_char_p, []),
@@ -161,6 +168,7 @@ HIP_SYMBOLS = {
                                   c_float, c_void_p]),
     "evc_attention_workspace_bytes": (c_longlong, [c_int, c_int, c_int, c_int]),
     "evc_attention_set_option": (c_int, [c_char_p, c_int]),
+    "evc_attention_plan_query": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(AttentionPlan)]),
     "evc_attention_ws_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                      c_float, c_void_p, c_void_p]),
     "evc_frame_group_norm_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_float, c_void_p]),
@@ -977,35 +985,75 @@ def conv_workspace_bytes(B, H, W, Ci, Co, KH, KW, splits=0, arith=None):
 
 def attention_set_option(name, value):
     """A/B switch of the attention kernels (include/evc_hip.h: "kv_planes", "f16_min_keys", "short_seq")."""
-    if hip_lib().evc_attention_set_option(name.encode(), int(value)) != 0:
+    if hip_lib(require_device=False).evc_attention_set_option(name.encode(), int(value)) != 0:
         raise EvcKernelError(f"unknown attention option {name!r}")
 
 
-def attention(qkv, C, heads, out=None, bounds=None, invariant=False):
+# Optional launch record (tests/attention_ledger.py): when a list is installed here ``attention`` appends the plan of the call
+# it is about to make, with (B, heads, N, D, with_bounds, invariant).
+ATTN_PROFILE = None
+
+
+def attention_plan(B, heads, N, D, with_bounds=False, have_ws=None, invariant=False):
+    """The whole plan of an attention launch without a launch (``evc_attention_plan_query``; works without a GPU): a dict of
+    the kernel instance, waves per workgroup, key parts, tiles per part, the K / V pre-pass, the merge launch, LDS and
+    workspace bytes.  ``have_ws=None``: as ``attention`` calls it, with a workspace exactly where the workspace size is not 0.
+    Raises ``EvcKernelError`` with the launch's error code for arguments the launch refuses."""
+    L = hip_lib(require_device=False)
+    if have_ws is None:
+        nbytes = (L.evc_attention_invariant_workspace_bytes if invariant else L.evc_attention_workspace_bytes)(B, heads, N, D)
+        have_ws = nbytes > 0
+    out = AttentionPlan()
+    _check(L.evc_attention_plan_query(B, heads, N, D, int(bool(with_bounds)), int(bool(have_ws)), int(bool(invariant)),
+                                      ctypes.byref(out)), "evc_attention_plan_query")
+    return dict(kernel=out.kernel.decode(), waves=out.waves, kparts=out.kparts, tiles_per_part=out.tiles_per_part,
+                kv_planes=bool(out.kv_planes), merge=bool(out.merge), short_seq=bool(out.short_seq),
+                lds_bytes=out.lds_bytes, parts_bytes=out.parts_bytes, ws_bytes=out.ws_bytes)
+
+
+def attention(qkv, C, heads, out=None, bounds=None, invariant=False, ws=None):
     """qkv: (B, N, 3C) with q | k | v concatenated along channels; returns (B, N, C).  ``bounds``: three int32 words
-    (element bounds of q, k, v from ``moments_bound``) select the fp16-split kernel; None the f32-MFMA one."""
+    (element bounds of q, k, v from ``moments_bound``) select the fp16-split kernel; None the f32-MFMA one.  ``out`` may be
+    wider than C: its last dimension is the row stride, columns from C on are left alone.  ``ws``: a float32 workspace of at
+    least the workspace bytes of the shape, instead of the shared one; False: ``evc_attention_f32``, the entry point without a
+    workspace (f32 kernel, never a key split; default mode only)."""
     L = hip_lib()
     B, N, ld = qkv.shape
     D = C // heads
+    inv = bool(invariant)
     if out is None:
         out = torch.empty((B, N, C), device=qkv.device, dtype=torch.float32)
+    ld_out = out.shape[-1]
+    assert out.is_contiguous() and tuple(out.shape[:2]) == (B, N) and ld_out >= C
     base = qkv.data_ptr()
-    if bool(invariant):      # plan from (heads, N, D) only; bounds: (B, 3) words
-        nbytes = L.evc_attention_invariant_workspace_bytes(B, heads, N, D)
-        ws = _workspace(nbytes, qkv.device) if nbytes > 0 else None
-        _check(L.evc_attention_invariant_f32(c_void_p(base), c_void_p(base + 4 * C), c_void_p(base + 8 * C), ld, fptr(out), C,
-                                             B, heads, N, D, float(int(D) ** (-0.5)),
+    nbytes = (L.evc_attention_invariant_workspace_bytes if inv else L.evc_attention_workspace_bytes)(B, heads, N, D)
+    if ws is None:
+        ws = _workspace(nbytes, qkv.device) if nbytes > 0 else None      # stream-ordered: shared with the conv workspace
+    elif ws is False:
+        assert bounds is None and not inv
+        ws = None
+        nbytes = -1
+    else:
+        assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() * 4 >= nbytes
+    if ATTN_PROFILE is not None:
+        ATTN_PROFILE.append(dict(attention_plan(B, heads, N, D, bounds is not None, ws is not None, inv),
+                                 call=(B, heads, N, D, bounds is not None, inv)))
+    if inv:      # plan from (heads, N, D) only; bounds: (B, 3) words
+        _check(L.evc_attention_invariant_f32(c_void_p(base), c_void_p(base + 4 * C), c_void_p(base + 8 * C), ld, fptr(out),
+                                             ld_out, B, heads, N, D, float(int(D) ** (-0.5)),
                                              None if bounds is None else _word(bounds, 3 * B), ptr(ws), stream_ptr()),
                "evc_attention_invariant_f32")
         return out
-    nbytes = L.evc_attention_workspace_bytes(B, heads, N, D)
-    ws = _workspace(nbytes, qkv.device) if nbytes > 0 else None      # stream-ordered: shared with the conv workspace
     if bounds is not None:
-        _check(L.evc_attention_f16x3_f32(c_void_p(base), c_void_p(base + 4 * C), c_void_p(base + 8 * C), ld, fptr(out), C,
+        _check(L.evc_attention_f16x3_f32(c_void_p(base), c_void_p(base + 4 * C), c_void_p(base + 8 * C), ld, fptr(out), ld_out,
                                          B, heads, N, D, float(int(D) ** (-0.5)), _word(bounds, 3), ptr(ws), stream_ptr()),
                "evc_attention_f16x3_f32")
         return out
-    _check(L.evc_attention_ws_f32(c_void_p(base), c_void_p(base + 4 * C), c_void_p(base + 8 * C), ld, fptr(out), C, B,
+    if nbytes < 0:
+        _check(L.evc_attention_f32(c_void_p(base), c_void_p(base + 4 * C), c_void_p(base + 8 * C), ld, fptr(out), ld_out, B,
+                                   heads, N, D, float(int(D) ** (-0.5)), stream_ptr()), "evc_attention_f32")
+        return out
+    _check(L.evc_attention_ws_f32(c_void_p(base), c_void_p(base + 4 * C), c_void_p(base + 8 * C), ld, fptr(out), ld_out, B,
                                   heads, N, D, float(int(D) ** (-0.5)), ptr(ws), stream_ptr()), "evc_attention_ws_f32")
     return out
 

@@ -335,6 +335,29 @@ int evc_attention_ws_f32(const float* q, const float* k, const float* v, int ld_
 int evc_attention_f16x3_f32(const float* q, const float* k, const float* v, int ld_qkv, float* out, int ld_out, int B,
                             int heads, int N, int D, float scale, const unsigned* bounds, float* ws, void* stream);
 
+/* The whole plan of an attention launch without a launch (no device needed): the kernel template instance as rocprofv3
+ * --kernel-trace prints it up to spacing ("attention_kernel<192,4>", "attention_f16_kernel<192,4,pre>",
+ * "attention_short_f16_kernel<64>"), waves per workgroup, key parts and 32-key tiles per part, whether
+ * attention_kv_planes_kernel writes K / V tile images first (kv_planes), whether attention_merge_kernel follows (merge), whether
+ * it is a short-sequence kernel, the kernel's dynamic LDS, the bytes of the key-part buffers at the head of the workspace (= the
+ * offset of the K / V tile images) and what evc_attention_workspace_bytes / evc_attention_invariant_workspace_bytes report for
+ * the shape.  The launches are made from the same resolved plan, so the answer is what runs.
+ *   invariant = 0, with_bounds = 0, have_ws = 0   evc_attention_f32
+ *   invariant = 0, with_bounds = 0, have_ws = 1   evc_attention_ws_f32 with a workspace
+ *   invariant = 0, with_bounds = 1                evc_attention_f16x3_f32, have_ws: with a workspace or with NULL
+ *   invariant = 1                                 evc_attention_invariant_f32, with_bounds: bounds given or NULL
+ * Default mode reflects the current evc_attention_set_option values, invariant mode ignores them.  Arguments the launch refuses
+ * give the launch's error code: EVC_EUNSUPPORTED for a head width outside the above, EVC_EINVAL for a size <= 0 and for
+ * have_ws = 0 where the entry point asks for a workspace (evc_attention_f16x3_f32 / evc_attention_invariant_f32 with
+ * workspace bytes > 0). */
+typedef struct {
+    char kernel[64];
+    int waves, kparts, tiles_per_part, kv_planes, merge, short_seq;
+    long long lds_bytes, parts_bytes, ws_bytes;
+} evc_attention_plan;
+int evc_attention_plan_query(int B, int heads, int N, int D, int with_bounds, int have_ws, int invariant,
+                             evc_attention_plan* out);
+
 /* ---- frame axis (pseudo-3-D score network, config.model.arch = unetmorepseudo3d) -----------------
  * Video activations are x[b][n][pixel][c]: an NHWC tensor of B*N images, the N frames of a sample adjacent.  A per-frame Conv2d
  * is then evc_conv2d_nhwc_f32 over B*N images; PseudoConv3d's Conv1d over the frames (reference models/better/layers3d.py:274,
