@@ -33,6 +33,8 @@ one more printed line and ``ssim_<idx>.npy`` / ``ssim_frames_<idx>.npy``; a repo
 ``--fid WEIGHTS.pth`` (pytorch-fid's Inception-v3 file, never fetched) adds the FID and the k-NN precision / recall (evaluation/;
 fid.py, csrc/inception.hip) of every job's 30 decoded frames against the original clip's: one more printed
 line and ``fid_<idx>.npy`` / ``fid_values_<idx>.npy`` / ``pr_values_<idx>.npy``; ``--fid-dims`` picks the Inception block.
+Every reported number is measured, printed and saved by report.py (``Measurer``, ``sender_lines``, ``Collector``); ``main`` parses
+and refuses, starts the ranks, loads weights and data, and runs ``run_mask_policy`` or ``run_policy_sweep``.
 """
 import argparse
 import os
@@ -43,6 +45,8 @@ import numpy as np
 import torch
 
 from .recovery import NumericsError  # noqa: F401  (raised by check_numerics and by the decoder's range recovery)
+from . import report as R
+from .report import cal_psnr  # noqa: F401  (defined there; importable from here as before)
 
 DEFAULT_PATHS = [f"checkpoints/neural network/{i}.pth.tar" for i in range(6)]
 
@@ -135,45 +139,26 @@ def build_parser():
                    help="also save psnr_yuv_frames_<idx>.npy and psnr_yuv_<idx>.npy: the PSNR of the reference's codec benchmark "
                         "(bench_uvg.py:487,508-509) -- original and decoded clip both go RGB -> 8-bit 4:2:0 -> RGB (bicubic) -> "
                         "rounded to 8 bits")
-    p.add_argument("--ssim", action="store_true",
-                   help="also report each job's SSIM against the original clip (fvd_utils/calculate_ssim.py: 11x11 Gaussian window, "
-                        "float64, mean over the valid region and the 3 channels) and save ssim_frames_<idx>.npy (jobs, 30) and "
-                        "ssim_<idx>.npy; with --yuv-metrics also ssim_yuv_frames_<idx>.npy and ssim_yuv_<idx>.npy, on the two 8-bit "
-                        "clips psnr_yuv compares.  A reported value only: no --policy decides by it")
     p.add_argument("--lpips-net", choices=["alex", "vgg", "squeeze"], default="alex",
                    help="lpips policy: the backbone whose weight files --metric names (the HIP LPIPS family, lpips.py); frames are "
                         "passed to it as they are, as with the default")
-    p.add_argument("--lpips", type=str, default=None, metavar="NET:BACKBONE.pth,LIN.pth",
-                   help="also report each job's LPIPS against the original clip as the reference's benchmark computes it "
-                        "(fvd_utils/calculate_lpips.py:9-58: frames mapped to [-1, 1], spatial map, its mean), under any --policy: "
-                        "NET = alex, vgg or squeeze, then torchvision's checkpoint of the backbone and lpips' weights/v0.1/NET.pth, "
-                        "or NET:ONE_SAVED_STATE_DICT.pth; prints one LPIPS(NET): line per job and saves lpips_NET_frames_<idx>.npy "
-                        "(jobs, 30) and lpips_NET_<idx>.npy (RD envelope, lower is better)")
-    add_fid_flags(p)
+    R.add_metric_flags(
+        p,
+        ssim_help="also report each job's SSIM against the original clip (fvd_utils/calculate_ssim.py: 11x11 Gaussian window, "
+                  "float64, mean over the valid region and the 3 channels) and save ssim_frames_<idx>.npy (jobs, 30) and "
+                  "ssim_<idx>.npy; with --yuv-metrics also ssim_yuv_frames_<idx>.npy and ssim_yuv_<idx>.npy, on the two 8-bit "
+                  "clips psnr_yuv compares.  A reported value only: no --policy decides by it",
+        lpips_help="also report each job's LPIPS against the original clip as the reference's benchmark computes it "
+                   "(fvd_utils/calculate_lpips.py:9-58: frames mapped to [-1, 1], spatial map, its mean), under any --policy: "
+                   "NET = alex, vgg or squeeze, then torchvision's checkpoint of the backbone and lpips' weights/v0.1/NET.pth, "
+                   "or NET:ONE_SAVED_STATE_DICT.pth; prints one LPIPS(NET): line per job and saves lpips_NET_frames_<idx>.npy "
+                   "(jobs, 30) and lpips_NET_<idx>.npy (RD envelope, lower is better)")
     return p
 
 
 YUV_FLAGS = ("data_yuv", "yuv_geometry", "yuv_upsample", "yuv_out", "yuv_metrics", "yuv_fit", "yuv_resize", "data_frames",
              "yuv_tile_overlap")
 OPT_IN_FLAGS = YUV_FLAGS + ("ssim", "lpips", "lpips_net", "fid", "fid_dims")       # written to args.yml only when used: a run without them leaves what it always left
-
-
-def add_fid_flags(p):
-    """--fid / --fid-dims of city_sender.py and city_receiver.py."""
-    p.add_argument("--fid", type=str, default=None, metavar="WEIGHTS.pth",
-                   help="pytorch-fid's pt_inception-2015-12-05-6726825d.pth (never fetched): also report each job's FID and k-NN "
-                        "precision / recall (k = 3) of the decoded clip's 30 frames against the original's, on the HIP Inception-v3 "
-                        "(evaluation/fid_PR.py, pr.py; fid.py, DESIGN.md section 8f); prints one 'FID: <v> precision: <p> recall: "
-                        "<r>' line per job and saves fid_<idx>.npy (RD envelope, lower is better), fid_values_<idx>.npy (jobs,) and "
-                        "pr_values_<idx>.npy (jobs, 2)")
-    p.add_argument("--fid-dims", type=int, choices=[64, 192, 768, 2048], default=2048,
-                   help="--fid: the Inception block whose features are compared (64, 192, 768: a map's spatial mean; default 2048)")
-
-
-def check_fid_flag(args):
-    """``--fid FILE`` must name a file; said before any GPU work."""
-    if args.fid and not os.path.isfile(args.fid):
-        sys.exit(f"--fid {args.fid}: no such file")
 
 
 def add_yuv_input_flags(p):
@@ -369,12 +354,6 @@ def recovery_note(dec):
     return ""
 
 
-def cal_psnr(a, b, maxvalue=1.0):
-    """city_sender.py:257-260."""
-    mse = np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)
-    return 10 * np.log10((maxvalue ** 2) / mse)
-
-
 def save_output(gt, xge, q, thr, idx, output_dir):
     """function.py:41-52 (npy always; png when PIL is importable -- the reference uses cv2)."""
     os.makedirs(output_dir, exist_ok=True)
@@ -388,26 +367,31 @@ def save_output(gt, xge, q, thr, idx, output_dir):
         pass
 
 
-def main(argv=None):
-    args = parse_args(argv)
-    if args.entropy_estimation and args.bitstream_dir:
-        sys.exit("--entropy-estimation with --bitstream-dir: an estimated rate comes without coded strings, so there is nothing "
-                 "to write into a bitstream; drop one of the two")
-    if args.lpips:
-        from .lpips import parse_spec
-        parse_spec(args.lpips)           # FileNotFoundError names a missing weight file before any GPU work
-    check_fid_flag(args)
-    import yaml
-    from . import dist as D
-    if D.needs_self_launch(args.gpus):      # parent: starts the ranks before any HIP call, relays their exit status
-        script = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "city_sender.py")
-        sys.exit(D.self_launch(script, sys.argv[1:] if argv is None else list(argv), args.gpus))
-    from . import ckpt, config as C, lib as L, sampler as S, synthetic
-    from .decoder import ClipDecoder
-    from .elic import ElicModel, inference
-    from .scorenet import build_score_network
+def diffusion_weights(args, cfg):
+    """The score network's state dict: ``checkpoint_<ckpt>.pt`` under --exp, else --synthetic's seeded stand-in, else exit."""
+    from . import ckpt, synthetic
+    ck = os.path.join(args.exp, f"checkpoint_{cfg.sampling.ckpt_id}.pt")
+    if os.path.exists(ck):
+        return ckpt.load_diffusion_checkpoint(ck, ema=cfg.model.ema)
+    if args.synthetic:
+        return synthetic.diffusion_state_dict(cfg, args.seed)
+    sys.exit(f"missing {ck} (pass --synthetic for seeded stand-in weights)")
 
-    resolve_policy(args, log=lambda m: print(m, flush=True))
+
+def elic_weights(args, paths, q, missing, density=False):
+    """The ELIC state dict of quality q: ``paths[q]``, else --synthetic's stand-in (density: with the density behind the
+    bottleneck's tables, which entropy estimation needs; the same weights either way), else exit with ``missing``."""
+    from . import ckpt, synthetic
+    if q < len(paths) and os.path.exists(paths[q]):
+        return ckpt.load_elic_state_dict(paths[q])
+    if args.synthetic:
+        return synthetic.elic_state_dict_with_density(q) if density else synthetic.elic_state_dict(q)
+    sys.exit(missing)
+
+
+def resolve_noise(args, say):
+    """What the resolved policy rules out among --batch-invariant, --share-generations, --bitstream-dir and --noise, and the
+    noise the sweep draws (``args.noise``)."""
     if args.batch_invariant:
         from .recovery import recovery_mode
         if args.policy == "mask":
@@ -419,7 +403,7 @@ def main(argv=None):
             sys.exit("--batch-invariant does not combine with --range-recovery layer: one sample's range event would demote "
                      "layers for every sample and for the rest of the run, and a receiver could not know which")
         if args.noise is None:
-            print("noise: evc (specification N1) because --batch-invariant frames are meant to be reproduced", flush=True)
+            say("noise: evc (specification N1) because --batch-invariant frames are meant to be reproduced")
             args.noise = "evc"
     if args.share_generations and args.policy == "mask":
         sys.exit("--share-generations applies to the psnr / lpips policy sweep (the mask policy has one job per clip)")
@@ -428,10 +412,170 @@ def main(argv=None):
             sys.exit("--bitstream-dir with --noise torch: a job stream whose frames depend on torch's generators cannot be "
                      "replayed by a receiver; drop --noise or pass --noise evc")
         if args.bitstream_dir and args.noise is None:
-            print("noise: evc (specification N1) because --bitstream-dir writes job streams a receiver must replay", flush=True)
+            say("noise: evc (specification N1) because --bitstream-dir writes job streams a receiver must replay")
             args.noise = "evc"
         args.noise = args.noise or "torch"
-    fvd_path = resolve_fvd(args, log=lambda m: print(m, flush=True))
+
+
+def write_run_files(args, raw):
+    """config.yml and args.yml of the run, where the reference writes them."""
+    import yaml
+    vf = os.path.join(args.exp, "video_samples", args.video_folder)
+    os.makedirs(vf, exist_ok=True)
+    with open(os.path.join(vf, "config.yml"), "w") as f:
+        yaml.dump(raw, f, default_flow_style=False)
+    with open(os.path.join(vf, "args.yml"), "w") as f:
+        defaults = vars(build_parser().parse_args([]))      # the opt-in flags appear only when used
+        yaml.dump({k: v for k, v in vars(args).items() if k not in OPT_IN_FLAGS or v != defaults[k]}, f, default_flow_style=False)
+
+
+def load_models(args, cfg, rank, world, device):
+    """-> (score network, {q: ElicModel}): rank 0 reads (or synthesises) the weights, one RCCL broadcast each."""
+    from . import dist as D
+    from .elic import ElicModel
+    from .scorenet import build_score_network
+    sd_d, sd_e = None, {}
+    if rank == 0:
+        sd_d = diffusion_weights(args, cfg)
+        sd_e = {q: elic_weights(args, args.paths, q, f"missing {args.paths[q]} (pass --synthetic)", args.entropy_estimation)
+                for q in args.q}
+    sd_d = D.broadcast_state_dict(sd_d, 0, device, world)
+    net = build_score_network(cfg, sd_d, device=device)     # model.arch: unetmore (default, + spade) | unetmorepseudo3d | unet
+    return net, {q: ElicModel(D.broadcast_state_dict(sd_e.get(q), 0, device, world), device=device) for q in args.q}
+
+
+def load_data(args, cfg, rank, log):
+    """-> (clips indexable by video, (30, 3, H, W) uint8 each; frame rate of written .y4m files)."""
+    if args.data_yuv or args.data_frames:
+        data, fps = load_yuv_clips(args, cfg.data.image_size, log=log)
+        if args.end_idx >= len(data):
+            sys.exit(f"{'--data_yuv ' + args.data_yuv if args.data_yuv else '--data_frames ' + args.data_frames} holds {len(data)} clip(s) of 30 frames; --end_idx {args.end_idx} is beyond them")
+        if args.yuv_fit == "tile" and rank == 0:
+            write_tile_manifests(args, cfg.data.image_size, len(data), fps, log=log)
+        return data, fps
+    if os.path.exists(args.data_npy):
+        return np.load(args.data_npy, mmap_mode="r"), 30
+    if args.synthetic:
+        from . import synthetic
+        return synthetic.make_clips(args.end_idx + 1, seed=args.seed), 30
+    sys.exit(f"missing {args.data_npy} (pass --synthetic)")
+
+
+def report_jobs(run, jobs, more=None):
+    """jobs: [(vid, q, thr, x, gt, bits, d)] that passed ``check_numerics``, x and gt numpy (30, 3, H, W).  They are measured
+    together (report.Measurer: one I3D pass for the call's clips); then, job by job, the lines are printed, city_output_npy /
+    .png / .y4m written and the values handed to the collector.  more: per job, values measured elsewhere."""
+    values = run.measurer.measure_jobs([(vid, x, gt) for vid, _, _, x, gt, _, _ in jobs])
+    for (vid, q, thr, x, gt, bits, d), v, extra in zip(jobs, values, more or [{}] * len(jobs)):
+        bpp = sum(bits) / 128 / 128 / 30
+        for line in R.sender_lines(v, d, bpp, run.measurer.net):
+            run.log(f"video {vid} q{q} thr {thr:.2f}: {line}")
+        out = os.path.join(run.args.output_path, f"output_{vid}")
+        save_output(np.concatenate(list(gt.transpose(0, 2, 3, 1)), axis=1), np.concatenate(list(x.transpose(0, 2, 3, 1)), axis=1),
+                    q, thr, vid, out)
+        if run.args.yuv_out:
+            from . import video_io as V
+            V.write_clip(os.path.join(out, "city_idx%d_q%d_thr%.2f.y4m" % (vid, q, thr)), x, run.fps)
+        run.collector.add(vid, bpp, {**v, **extra})
+
+
+def run_mask_policy(run, net, models, cfg, data, vids, device, gen):
+    """Every clip has the same transmit mask (2 key frames, then generated): decode ``--batch`` clips per launch through the
+    receiver (the path bench.py measures) instead of one clip at a time."""
+    from . import sampler as S
+    from .decoder import ClipDecoder, all_generated_mask
+    from .elic import count_bits
+    args = run.args
+    mask = all_generated_mask()
+    for q in args.q:
+        model = models[q]
+        dec = ClipDecoder(net, model, cfg, S.get_sampler(args.sampler), groups=args.groups,
+                          range_recovery=args.range_recovery, log=run.log)
+        for b0 in range(0, len(vids), max(1, args.batch)):
+            chunk = vids[b0:b0 + max(1, args.batch)]
+            gt = torch.from_numpy(np.stack([np.asarray(data[v], dtype=np.float32) / 255.0 for v in chunk]))
+            keys, shape, est_bits = [], None, []
+            key_frames = [] if args.entropy_estimation else None
+            for f in (0, 1):                                   # key frames (city_sender.py:521-524), batched
+                pad = (-gt.shape[-1]) % args.patch, (-gt.shape[-2]) % args.patch
+                xk = torch.nn.functional.pad(gt[:, f], (0, pad[0], 0, pad[1]))
+                if args.entropy_estimation:                    # no strings: the decoder is handed the frames themselves
+                    est = model.estimate(xk.to(device))
+                    key_frames.append(est["x_hat"])
+                    est_bits.append((est["bits_y"] + est["bits_z"]).tolist())
+                    continue
+                enc = model.compress(xk.to(device))
+                keys.append(enc["strings"]); shape = enc["shape"]
+            d_rx, keys_rx, shape_rx = mask, keys, shape
+            if args.bitstream_dir:                             # sender -> file -> receiver
+                from . import container
+                os.makedirs(args.bitstream_dir, exist_ok=True)
+                path = os.path.join(args.bitstream_dir, f"clips_{chunk[0]}_{chunk[-1]}_q{q}.evc")
+                with open(path, "wb") as fh:
+                    fh.write(container.pack(mask, keys, shape, codec=model.codec_tag()))
+                with open(path, "rb") as fh:          # refuses a stream coded under another arithmetic
+                    d_rx, keys_rx, shape_rx = container.unpack(fh.read(), expect_codec=model.codec_tag())
+            frames = dec.decode(d_rx, keys_rx, shape_rx, generator=gen, key_frames=key_frames)[..., :gt.shape[-2], :gt.shape[-1]]
+            check_numerics(frames, f"videos {chunk[0]}..{chunk[-1]} q{q}", recovery_note(dec))
+            x_all = frames.cpu().numpy()
+            bits = [[b[j] for b in est_bits] if args.entropy_estimation else
+                    [count_bits([[[[p[j]] for p in sl] for sl in k[0]], [k[1][j]]]) for k in keys] for j in range(len(chunk))]
+            report_jobs(run, [(vid, q, 0.0, x_all[j], gt[j].numpy(), bits[j], mask) for j, vid in enumerate(chunk)])
+
+
+def run_policy_sweep(run, net, models, cfg, data, vids, device):
+    """city_sender.py:495-607 batched (policy.py): every (video, q, threshold) job of this rank advances in lockstep,
+    ``--policy-batch`` jobs per score-network launch; key frames coded once per (video, q, frame)."""
+    from . import policy as P, sampler as S
+    from .decoder import ClipDecoder
+    args = run.args
+    if args.policy == "lpips":       # city_sender.py:508: np.arange(0.30, 0.02, -0.01) rounded to 2 decimals
+        thresholds = args.thresholds or [float("%.2f" % t) for t in np.arange(0.30, 0.02, -0.01)]
+    else:
+        thresholds = args.thresholds or [0.0]
+    metric = P.load_metric(args.policy, args.metric, device, net=args.lpips_net)
+    dec = ClipDecoder(net, None, cfg, S.get_sampler(args.sampler), range_recovery=args.range_recovery, log=run.log)
+    clips = {vid: torch.from_numpy(np.asarray(data[vid], dtype=np.float32) / 255.0) for vid in vids}
+    shared = dict(noise_streams="group", share=True, stats={}) if args.share_generations else {}
+    res = P.run_policy(dec, models, clips, args.q, thresholds, metric, patch=args.patch, max_batch=args.policy_batch,
+                       seed=args.seed, device=device, bpp_limit=args.bpp_limit, log=run.log,
+                       noise=args.noise, batch_invariant=args.batch_invariant, estimate=args.entropy_estimation, **shared)
+    if shared:
+        st = shared["stats"]
+        run.log(f"shared generations: {sum(st['states'])} sample-rounds generated for {sum(st['jobs_served'])} "
+                f"job-rounds served ({len(st['states'])} rounds)")
+    if args.bitstream_dir:       # one replayable stream per reported job (receiver.py decodes them)
+        from .receiver import write_job_streams
+        written = write_job_streams(args.bitstream_dir, res, models, args.sampler, cfg)
+        run.log(f"wrote {len(written)} job stream(s) to {args.bitstream_dir}")
+    for vid in vids:
+        for q in args.q:
+            for r in res[(vid, q)]:
+                check_numerics(r["x"], f"video {vid} q{q} thr {r['thr']:.2f}", recovery_note(dec))
+            more = None
+            if args.policy == "lpips":      # per-frame distances of the decoded clip (city_sender.py:570-571)
+                more = [{"policy_lpips": metric.values(torch.from_numpy(r["x"]).to(device), clips[vid].to(device))}
+                        for r in res[(vid, q)]]
+            report_jobs(run, [(vid, q, r["thr"], r["x"], clips[vid].numpy(), r["bits"], r["d"]) for r in res[(vid, q)]], more)
+
+
+def main(argv=None):
+    # ---- parse and refuse: everything that can be said before any GPU work ----
+    args = parse_args(argv)
+    if args.entropy_estimation and args.bitstream_dir:
+        sys.exit("--entropy-estimation with --bitstream-dir: an estimated rate comes without coded strings, so there is nothing "
+                 "to write into a bitstream; drop one of the two")
+    R.check_metric_flags(args)
+    from . import dist as D
+    if D.needs_self_launch(args.gpus):      # parent: starts the ranks before any HIP call, relays their exit status
+        script = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "city_sender.py")
+        sys.exit(D.self_launch(script, sys.argv[1:] if argv is None else list(argv), args.gpus))
+    from types import SimpleNamespace
+    from . import config as C, lib as L
+    say = lambda m: print(m, flush=True)  # noqa: E731
+    resolve_policy(args, log=say)
+    resolve_noise(args, say)
+    fvd_path = resolve_fvd(args, log=say)
     cfg, raw = C.load_config(args.config, args.config_mod)
     if args.subsample is not None:
         cfg.sampling.subsample = args.subsample
@@ -440,240 +584,29 @@ def main(argv=None):
     if args.gpus > 1 and world != args.gpus:
         sys.exit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     L.hip_lib()
-    i3d = None
-    if fvd_path:
-        from . import fvd as FV
-        i3d = FV.I3d.from_file(fvd_path, device=device)
-    lp = None
-    if args.lpips:
-        from .lpips import Lpips
-        lp = Lpips.from_spec(args.lpips, device=device)
-    inception = None
+    # ---- weights and data ----
+    nets = R.load_networks(args, device, fvd_path)
     if args.fid:
-        from . import fid as FI
-        inception = FI.InceptionV3.from_file(args.fid, device=device, max_images=30)
-        print(f"Inception-v3 weights of --fid: {args.fid} (features: {args.fid_dims})", flush=True)
+        say(f"Inception-v3 weights of --fid: {args.fid} (features: {args.fid_dims})")
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
-    vf = os.path.join(args.exp, "video_samples", args.video_folder)
     if rank == 0:
-        os.makedirs(vf, exist_ok=True)
-        with open(os.path.join(vf, "config.yml"), "w") as f:
-            yaml.dump(raw, f, default_flow_style=False)
-        with open(os.path.join(vf, "args.yml"), "w") as f:
-            defaults = vars(build_parser().parse_args([]))      # the YUV flags and --ssim appear only when used
-            yaml.dump({k: v for k, v in vars(args).items() if k not in OPT_IN_FLAGS or v != defaults[k]}, f, default_flow_style=False)
-
-    # ---- weights: rank 0 reads (or synthesises) them, one RCCL broadcast each ----
-    sd_d, sd_e = None, {}
-    if rank == 0:
-        ck = os.path.join(args.exp, f"checkpoint_{cfg.sampling.ckpt_id}.pt")
-        if os.path.exists(ck):
-            sd_d = ckpt.load_diffusion_checkpoint(ck, ema=cfg.model.ema)
-        elif args.synthetic:
-            sd_d = synthetic.diffusion_state_dict(cfg, args.seed)
-        else:
-            sys.exit(f"missing {ck} (pass --synthetic for seeded stand-in weights)")
-        for q in args.q:
-            pth = args.paths[q]
-            if os.path.exists(pth):
-                sd_e[q] = ckpt.load_elic_state_dict(pth)
-            elif args.synthetic:
-                # the same weights either way; estimation also needs the density behind the bottleneck's tables
-                sd_e[q] = synthetic.elic_state_dict_with_density(q) if args.entropy_estimation else synthetic.elic_state_dict(q)
-            else:
-                sys.exit(f"missing {pth} (pass --synthetic)")
-    sd_d = D.broadcast_state_dict(sd_d, 0, device, world)
-    net = build_score_network(cfg, sd_d, device=device)     # model.arch: unetmore (default, + spade) | unetmorepseudo3d | unet
-    models = {q: ElicModel(D.broadcast_state_dict(sd_e.get(q), 0, device, world), device=device) for q in args.q}
-
-    yuv_fps = 30
-    if args.data_yuv or args.data_frames:
-        data, yuv_fps = load_yuv_clips(args, cfg.data.image_size, log=lambda m: print(f"[rank {rank}] {m}", flush=True))
-        if args.end_idx >= len(data):
-            sys.exit(f"{'--data_yuv ' + args.data_yuv if args.data_yuv else '--data_frames ' + args.data_frames} holds {len(data)} clip(s) of 30 frames; --end_idx {args.end_idx} is beyond them")
-        if args.yuv_fit == "tile" and rank == 0:
-            write_tile_manifests(args, cfg.data.image_size, len(data), yuv_fps, log=lambda m: print(f"[rank {rank}] {m}", flush=True))
-    elif os.path.exists(args.data_npy):
-        data = np.load(args.data_npy, mmap_mode="r")
-    elif args.synthetic:
-        data = synthetic.make_clips(args.end_idx + 1, seed=args.seed)
-    else:
-        sys.exit(f"missing {args.data_npy} (pass --synthetic)")
-
+        write_run_files(args, raw)
+    net, models = load_models(args, cfg, rank, world, device)
+    log = lambda m: print(f"[rank {rank}] {m}", flush=True)  # noqa: E731
+    data, yuv_fps = load_data(args, cfg, rank, log)
+    # ---- this rank's videos under one of the two policies ----
     lo, hi = D.shard_range(args.end_idx + 1 - args.start_idx, rank, world)
-    gen = torch.Generator(device=device).manual_seed(args.seed + rank)
-    if args.policy == "lpips":       # city_sender.py:508: np.arange(0.30, 0.02, -0.01) rounded to 2 decimals
-        thresholds = args.thresholds or [float("%.2f" % t) for t in np.arange(0.30, 0.02, -0.01)]
-    else:
-        thresholds = args.thresholds if args.policy == "psnr" and args.thresholds else [0.0]
-    t_start = time.time()
     vids = list(range(args.start_idx + lo, args.start_idx + hi))
-
-    gt_feats, fvd_store, yuv_store, ssim_store, ssim_yuv_store, lpips_store = {}, {}, {}, {}, {}, {}
-    fid_gt, fid_store = {}, {}
-
-    def job_fvds(jobs):
-        """FVD of each decoded clip against its video's original, as city_sender.py:575-577 computes it: calculate_fvd of
-        x_ge.repeat(2) against x_gt.repeat(2).  jobs: [(vid, x, gt)] numpy (30, 3, H, W).  I3D runs once per original video
-        and once per decoded clip, all clips of the call batched."""
-        if i3d is None:
-            return [None] * len(jobs)
-        new = {vid: gt for vid, _, gt in jobs if vid not in gt_feats}
-        if new:
-            for vid, f in zip(new, i3d(torch.from_numpy(np.stack(list(new.values())))).double().cpu().numpy()):
-                gt_feats[vid] = f
-        fx = i3d(torch.from_numpy(np.stack([x for _, x, _ in jobs]))).double().cpu().numpy()
-        return [FV.frechet_distance(np.stack([f, f]), np.stack([gt_feats[vid], gt_feats[vid]]))
-                for f, (vid, _, _) in zip(fx, jobs)]
-
-    def report(vid, q, thr, x, gt, bits, d, store, fvd=None):
-        bpp = sum(bits) / 128 / 128 / 30
-        ps = [cal_psnr(x[i], gt[i]) for i in range(30)]
-        print(f"[rank {rank}] video {vid} q{q} thr {thr:.2f}: d={[int(v) for v in d[:30]]} BPP {bpp:.5f} PSNR {np.mean(ps):.3f}",
-              flush=True)
-        if fvd is not None:
-            print(f"[rank {rank}] video {vid} q{q} thr {thr:.2f}: FVD: {fvd:f}", flush=True)
-            fvd_store.setdefault(vid, []).append(fvd)
-        store.setdefault(vid, ([], []))
-        store[vid][0].append(ps); store[vid][1].append(bpp)
-        g = np.concatenate(list(gt.transpose(0, 2, 3, 1)), axis=1)
-        xg = np.concatenate(list(x.transpose(0, 2, 3, 1)), axis=1)
-        save_output(g, xg, q, thr, vid, os.path.join(args.output_path, f"output_{vid}"))
-        if args.yuv_out:
-            from . import video_io as V
-            V.write_clip(os.path.join(args.output_path, f"output_{vid}", "city_idx%d_q%d_thr%.2f.y4m" % (vid, q, thr)), x, yuv_fps)
-        if args.ssim:
-            from .ssim import ssim_frames
-            ss = ssim_frames(x, gt)
-            print(f"[rank {rank}] video {vid} q{q} thr {thr:.2f}: SSIM: {np.mean(ss):.5f}", flush=True)
-            ssim_store.setdefault(vid, []).append(ss)
-        if lp is not None:           # the benchmark's LPIPS (calculate_lpips.py:35-58), one value per frame
-            lv = lp.spatial_mean(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)),
-                                 torch.from_numpy(np.ascontiguousarray(gt, dtype=np.float32))).double().cpu().numpy()
-            print(f"[rank {rank}] video {vid} q{q} thr {thr:.2f}: LPIPS({lp.net}): {np.mean(lv):.5f}", flush=True)
-            lpips_store.setdefault(vid, []).append(lv)
-        if inception is not None:    # FID and precision / recall of the clip's frames against the original's (fid_PR.py, pr.py)
-            if vid not in fid_gt:    # the originals' features: once per video
-                fid_gt[vid] = FI.features(torch.from_numpy(np.ascontiguousarray(gt, dtype=np.float32)), inception, args.fid_dims)
-            fx = FI.features(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)), inception, args.fid_dims)
-            fv, pv, rv = FI.fid_and_pr(fid_gt[vid], fx, k=3)
-            print(f"[rank {rank}] video {vid} q{q} thr {thr:.2f}: FID: {fv:f} precision: {pv:.5f} recall: {rv:.5f}", flush=True)
-            fid_store.setdefault(vid, []).append((fv, pv, rv))
-        if args.yuv_metrics:
-            from . import video_io as V
-            pair = V.yuv_metric_clips(x, gt)
-            yuv_store.setdefault(vid, []).append(V.psnr_yuv(x, gt, clips=pair))
-            if args.ssim:
-                ssim_yuv_store.setdefault(vid, []).append(V.ssim_yuv(x, gt, clips=pair))
-
-    store = {}
+    gen = torch.Generator(device=device).manual_seed(args.seed + rank)
+    t_start = time.time()
+    run = SimpleNamespace(args=args, log=log, fps=yuv_fps, measurer=R.Measurer(ssim=args.ssim, fid_dims=args.fid_dims, yuv=args.yuv_metrics, **nets))
+    run.collector = R.Collector(net=run.measurer.net)
     if args.policy == "mask":
-        # every clip has the same transmit mask (2 key frames, then generated): decode `--batch` clips per launch
-        # through the receiver (the path bench.py measures) instead of one clip at a time
-        from .decoder import all_generated_mask
-        from .elic import count_bits
-        mask = all_generated_mask()
-        for q in args.q:
-            model = models[q]
-            dec = ClipDecoder(net, model, cfg, S.get_sampler(args.sampler), groups=args.groups,
-                              range_recovery=args.range_recovery, log=lambda m: print(f"[rank {rank}] {m}", flush=True))
-            for b0 in range(0, len(vids), max(1, args.batch)):
-                chunk = vids[b0:b0 + max(1, args.batch)]
-                gt = torch.from_numpy(np.stack([np.asarray(data[v], dtype=np.float32) / 255.0 for v in chunk]))
-                keys, shape, est_bits = [], None, []
-                key_frames = [] if args.entropy_estimation else None
-                for f in (0, 1):                                   # key frames (city_sender.py:521-524), batched
-                    pad = (-gt.shape[-1]) % args.patch, (-gt.shape[-2]) % args.patch
-                    xk = torch.nn.functional.pad(gt[:, f], (0, pad[0], 0, pad[1]))
-                    if args.entropy_estimation:                    # no strings: the decoder is handed the frames themselves
-                        est = model.estimate(xk.to(device))
-                        key_frames.append(est["x_hat"])
-                        est_bits.append((est["bits_y"] + est["bits_z"]).tolist())
-                        continue
-                    enc = model.compress(xk.to(device))
-                    keys.append(enc["strings"]); shape = enc["shape"]
-                d_rx, keys_rx, shape_rx = mask, keys, shape
-                if args.bitstream_dir:                             # sender -> file -> receiver
-                    from . import container
-                    os.makedirs(args.bitstream_dir, exist_ok=True)
-                    path = os.path.join(args.bitstream_dir, f"clips_{chunk[0]}_{chunk[-1]}_q{q}.evc")
-                    with open(path, "wb") as fh:
-                        fh.write(container.pack(mask, keys, shape, codec=model.codec_tag()))
-                    with open(path, "rb") as fh:          # refuses a stream coded under another arithmetic
-                        d_rx, keys_rx, shape_rx = container.unpack(fh.read(), expect_codec=model.codec_tag())
-                frames = dec.decode(d_rx, keys_rx, shape_rx, generator=gen, key_frames=key_frames)[..., :gt.shape[-2], :gt.shape[-1]]
-                check_numerics(frames, f"videos {chunk[0]}..{chunk[-1]} q{q}", recovery_note(dec))
-                x_all = frames.cpu().numpy()
-                fvds = job_fvds([(vid, x_all[j], gt[j].numpy()) for j, vid in enumerate(chunk)])
-                for j, vid in enumerate(chunk):
-                    bits = [b[j] for b in est_bits] if args.entropy_estimation else \
-                        [count_bits([[[[p[j]] for p in sl] for sl in k[0]], [k[1][j]]]) for k in keys]
-                    report(vid, q, 0.0, x_all[j], gt[j].numpy(), bits, mask, store, fvds[j])
+        run_mask_policy(run, net, models, cfg, data, vids, device, gen)
     else:
-        # city_sender.py:495-607 batched (policy.py): every (video, q, threshold) job of this rank advances in lockstep,
-        # `--policy-batch` jobs per score-network launch; key frames coded once per (video, q, frame).
-        from . import policy as P
-        metric = P.load_metric(args.policy, args.metric, device, net=args.lpips_net)
-        dec = ClipDecoder(net, None, cfg, S.get_sampler(args.sampler), range_recovery=args.range_recovery,
-                          log=lambda m: print(f"[rank {rank}] {m}", flush=True))
-        clips = {vid: torch.from_numpy(np.asarray(data[vid], dtype=np.float32) / 255.0) for vid in vids}
-        shared = dict(noise_streams="group", share=True, stats={}) if args.share_generations else {}
-        res = P.run_policy(dec, models, clips, args.q, thresholds, metric, patch=args.patch, max_batch=args.policy_batch,
-                           seed=args.seed, device=device, bpp_limit=args.bpp_limit, log=lambda m: print(f"[rank {rank}] {m}", flush=True),
-                           noise=args.noise, batch_invariant=args.batch_invariant, estimate=args.entropy_estimation, **shared)
-        if shared:
-            st = shared["stats"]
-            print(f"[rank {rank}] shared generations: {sum(st['states'])} sample-rounds generated for {sum(st['jobs_served'])} "
-                  f"job-rounds served ({len(st['states'])} rounds)", flush=True)
-        if args.bitstream_dir:       # one replayable stream per reported job (receiver.py decodes them)
-            from .receiver import write_job_streams
-            written = write_job_streams(args.bitstream_dir, res, models, args.sampler, cfg)
-            print(f"[rank {rank}] wrote {len(written)} job stream(s) to {args.bitstream_dir}", flush=True)
-        metric_vals = {}
-        for vid in vids:
-            for q in args.q:
-                for r in res[(vid, q)]:
-                    check_numerics(r["x"], f"video {vid} q{q} thr {r['thr']:.2f}", recovery_note(dec))
-                fvds = job_fvds([(vid, r["x"], clips[vid].numpy()) for r in res[(vid, q)]]) if res[(vid, q)] else []
-                for r, fvd in zip(res[(vid, q)], fvds):
-                    report(vid, q, r["thr"], r["x"], clips[vid].numpy(), r["bits"], r["d"], store, fvd)
-                    if args.policy == "lpips":      # per-frame distances of the decoded clip (city_sender.py:570-571)
-                        v = metric.values(torch.from_numpy(r["x"]).to(device), clips[vid].to(device))
-                        metric_vals.setdefault(vid, []).append(v)
-        for vid, vals in metric_vals.items():
-            out_root = os.path.join(args.output_path, f"output_{vid}")
-            np.save(os.path.join(out_root, f"lpips_frames_{vid}.npy"), np.asarray(vals))
-            np.save(os.path.join(out_root, f"lpips_{vid}.npy"),
-                    P.rd_envelope(store[vid][1], np.mean(np.asarray(vals), 1), higher_is_better=False))
-    for vid, (ps, bpps) in store.items():
-        out_root = os.path.join(args.output_path, f"output_{vid}")
-        os.makedirs(out_root, exist_ok=True)
-        # reference names (function.py:148-230): psnr_<idx>.npy = RD envelope [bpp; mean PSNR] of the video's sweep;
-        # the raw sweep is kept beside it (per-threshold per-frame PSNR, per-threshold bpp)
-        from .policy import rd_envelope
-        np.save(os.path.join(out_root, f"psnr_{vid}.npy"), rd_envelope(bpps, np.mean(np.asarray(ps), 1), True))
-        np.save(os.path.join(out_root, f"psnr_frames_{vid}.npy"), np.asarray(ps))
-        np.save(os.path.join(out_root, f"bpp_{vid}.npy"), np.asarray(bpps))
-        if vid in yuv_store:     # the codec benchmark's PSNR (bench_uvg.py:487,508-509), laid out as psnr_<idx>.npy
-            np.save(os.path.join(out_root, f"psnr_yuv_{vid}.npy"), rd_envelope(bpps, np.mean(np.asarray(yuv_store[vid]), 1), True))
-            np.save(os.path.join(out_root, f"psnr_yuv_frames_{vid}.npy"), np.asarray(yuv_store[vid]))
-        for name, kept in (("ssim", ssim_store), ("ssim_yuv", ssim_yuv_store)):      # --ssim: laid out as psnr_<idx>.npy
-            if vid in kept:
-                np.save(os.path.join(out_root, f"{name}_{vid}.npy"), rd_envelope(bpps, np.mean(np.asarray(kept[vid]), 1), True))
-                np.save(os.path.join(out_root, f"{name}_frames_{vid}.npy"), np.asarray(kept[vid]))
-        if vid in lpips_store:   # --lpips NET:...: laid out as psnr_<idx>.npy, lower is better
-            np.save(os.path.join(out_root, f"lpips_{lp.net}_{vid}.npy"),
-                    rd_envelope(bpps, np.mean(np.asarray(lpips_store[vid]), 1), False))
-            np.save(os.path.join(out_root, f"lpips_{lp.net}_frames_{vid}.npy"), np.asarray(lpips_store[vid]))
-        if vid in fid_store:     # --fid: the envelope laid out as psnr_<idx>.npy, lower is better; raw values beside it
-            vals = np.asarray(fid_store[vid])
-            np.save(os.path.join(out_root, f"fid_{vid}.npy"), rd_envelope(bpps, vals[:, 0], False))
-            np.save(os.path.join(out_root, f"fid_values_{vid}.npy"), vals[:, 0])
-            np.save(os.path.join(out_root, f"pr_values_{vid}.npy"), vals[:, 1:])
-        if vid in fvd_store:     # reference name fvd_<idx>.npy: RD envelope [bpp; FVD], lower is better; raw values beside it
-            np.save(os.path.join(out_root, f"fvd_{vid}.npy"), rd_envelope(bpps, np.asarray(fvd_store[vid]), False))
-            np.save(os.path.join(out_root, f"fvd_values_{vid}.npy"), np.asarray(fvd_store[vid]))
+        run_policy_sweep(run, net, models, cfg, data, vids, device)
+    run.collector.save(args.output_path)
     D.barrier()
     if rank == 0:
         print(f"done in {time.time() - t_start:.1f}s")
@@ -681,3 +614,4 @@ def main(argv=None):
 
 if __name__ == "__main__":
     main()
+

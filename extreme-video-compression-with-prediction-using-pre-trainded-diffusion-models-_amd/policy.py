@@ -33,12 +33,7 @@ import torch
 
 from . import lib as L
 from .elic import count_bits
-
-
-def cal_psnr(a, b, maxvalue=1.0):
-    """city_sender.py:257-260 (float64)."""
-    mse = np.mean((np.asarray(a, dtype=np.float64) - np.asarray(b, dtype=np.float64)) ** 2)
-    return 10 * np.log10((maxvalue ** 2) / mse)
+from .report import cal_psnr
 
 
 class PsnrMetric:

@@ -10,7 +10,8 @@ The reference has no receiver (its generator runs inside the sender, city_sender
 ``ClipDecoder.decode_jobs``: the stream carries the job's program -- which frames are key frames, where each generation round
 was cut -- and the key of its noise (noise specification N1), so the receiver generates from the same
 decoded frames, in the same chunks, with the same noise as the sender judged.  The sampler, its step count and the denoise
-flag are read from the streams; only the ELIC models the streams name are loaded.  One process, one GPU.
+flag are read from the streams; only the ELIC models the streams name are loaded.  One process, one GPU.  With the original
+clips present each job's line carries its PSNR (``--ssim``, ``--lpips``: and those) and ``--fid`` adds a line, all from report.py.
 """
 import argparse
 import glob
@@ -120,23 +121,19 @@ def build_parser():
     p.add_argument("--yuv", action="store_true",
                    help="also write decoded_v<vid>_q<q>_thr<thr>.y4m (8-bit 4:2:0, full-range BT.709) beside each .npy")
     p.add_argument("--fps", type=str, default="30", help="--yuv: frame rate of the written files (30, 29.97 or 30000/1001)")
-    p.add_argument("--ssim", action="store_true",
-                   help="when the original clips are present, also print each job's SSIM (city_sender.py --ssim) after its PSNR")
-    p.add_argument("--lpips", type=str, default=None, metavar="NET:BACKBONE.pth,LIN.pth",
-                   help="when the original clips are present, also print each job's LPIPS (city_sender.py --lpips: NET = alex, vgg "
-                        "or squeeze; frames mapped to [-1, 1], mean of the spatial map) after its PSNR / SSIM")
-    from .cli import add_fid_flags
-    add_fid_flags(p)             # --fid / --fid-dims: with the original clips present, one FID / precision / recall line per job
+    from .report import add_metric_flags
+    add_metric_flags(            # with the original clips present: parts of the job's line, and one FID / precision / recall line
+        p,
+        ssim_help="when the original clips are present, also print each job's SSIM (city_sender.py --ssim) after its PSNR",
+        lpips_help="when the original clips are present, also print each job's LPIPS (city_sender.py --lpips: NET = alex, vgg "
+                   "or squeeze; frames mapped to [-1, 1], mean of the spatial map) after its PSNR / SSIM")
     return p
 
 
 def main(argv=None):
-    from . import ckpt, cli, config as C, lib as L, synthetic
+    from . import cli, config as C, lib as L, report as R
     args = cli.parse_args(argv, build_parser())
-    if args.lpips:
-        from .lpips import parse_spec
-        parse_spec(args.lpips)           # FileNotFoundError names a missing weight file before any GPU work
-    cli.check_fid_flag(args)
+    R.check_metric_flags(args)
     from .elic import ElicModel
     from .scorenet import build_score_network
     paths = args.paths or cli.DEFAULT_PATHS
@@ -147,29 +144,12 @@ def main(argv=None):
     cfg.sampling.ckpt_id = args.ckpt or cfg.sampling.ckpt_id
     device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cuda"
     L.hip_lib()
-    ck = os.path.join(args.exp, f"checkpoint_{cfg.sampling.ckpt_id}.pt")
-    if os.path.exists(ck):
-        sd_d = ckpt.load_diffusion_checkpoint(ck, ema=cfg.model.ema)
-    elif args.synthetic:
-        sd_d = synthetic.diffusion_state_dict(cfg, args.seed)
-    else:
-        sys.exit(f"missing {ck} (pass --synthetic for seeded stand-in weights)")
-    net = build_score_network(cfg, sd_d, device=device)
-    lp = None
-    if args.lpips:
-        from .lpips import Lpips
-        lp = Lpips.from_spec(args.lpips, device=device)
-    inception, fid_gt = None, {}
-    if args.fid:
-        from . import fid as FI
-        inception = FI.InceptionV3.from_file(args.fid, device=device, max_images=30)
+    net = build_score_network(cfg, cli.diffusion_weights(args, cfg), device=device)
+    nets = R.load_networks(args, device)
+    measurer = R.Measurer(ssim=args.ssim, fid_dims=args.fid_dims, **nets)
 
     def model_for(q):
-        if q < len(paths) and os.path.exists(paths[q]):
-            return ElicModel(ckpt.load_elic_state_dict(paths[q]), device=device)
-        if args.synthetic:
-            return ElicModel(synthetic.elic_state_dict(q), device=device)
-        sys.exit(f"missing ELIC checkpoint for q{q} (pass --synthetic)")
+        return ElicModel(cli.elic_weights(args, paths, q, f"missing ELIC checkpoint for q{q} (pass --synthetic)"), device=device)
 
     log = lambda m: print(m, flush=True)  # noqa: E731
     stats = {}
@@ -193,27 +173,14 @@ def main(argv=None):
         if args.yuv:
             from . import video_io as V
             V.write_clip(os.path.join(args.output_path, f"decoded_{name}.y4m"), x, args.fps)
-        line = f"{os.path.basename(path)}: {job['frames']} frames, {int(job['d'].sum())} key frames, " \
-               f"{container.payload_bits(job['key_strings'])} bits, {job['sampler']}-{job['subsample']}"
+        values = {}
         if data is not None:
-            gt = np.asarray(data[job["vid"]], dtype=np.float32) / 255.0
-            line += " PSNR %.3f" % np.mean([cli.cal_psnr(x[t], gt[t]) for t in range(len(x))])
-            if args.ssim:
-                from .ssim import ssim_frames
-                line += " SSIM %.5f" % np.mean(ssim_frames(np.ascontiguousarray(x, dtype=np.float32), gt[:len(x)]))
-            if lp is not None:
-                v = lp.spatial_mean(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)), torch.from_numpy(gt[:len(x)]))
-                line += " LPIPS(%s) %.5f" % (lp.net, float(v.double().mean()))
-        same = frames_match(job, x)
-        if same is not None:             # format 4: the receiver's frames against the sender's checksum
-            line += ", frames: match" if same else ", frames: MISMATCH"
-            mismatches += 0 if same else 1
-        log(line)
-        if inception is not None and data is not None:       # city_sender.py --fid's line, the originals' features once per video
-            if job["vid"] not in fid_gt:
-                fid_gt[job["vid"]] = FI.features(torch.from_numpy(gt[:len(x)]), inception, args.fid_dims)
-            fx = FI.features(torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)), inception, args.fid_dims)
-            log("%s: FID: %f precision: %.5f recall: %.5f" % ((os.path.basename(path),) + FI.fid_and_pr(fid_gt[job["vid"]], fx, k=3)))
+            values = measurer.measure(job["vid"], x, (np.asarray(data[job["vid"]], dtype=np.float32) / 255.0)[:len(x)])
+        same = frames_match(job, x)      # format 4: the receiver's frames against the sender's checksum
+        mismatches += same is False
+        for line in R.receiver_lines(os.path.basename(path), job["frames"], int(job["d"].sum()), container.payload_bits(job["key_strings"]),
+                                     job["sampler"], job["subsample"], values, measurer.net, same):
+            log(line)
     log(f"decoded {len(jobs)} job stream(s) into {args.output_path}")
     if mismatches:
         sys.exit(f"{mismatches} job(s) decoded to other frames than the sender's (frames: MISMATCH)")

@@ -106,7 +106,7 @@ def main(argv=None):
     if args.data_yuv and args.data_frames:
         sys.exit("--data_frames replaces --data_yuv: pass one of them")
     import torch
-    from . import cli, lib as L, video_io as V
+    from . import lib as L, report as R, video_io as V
     from .recovery import NumericsError
     log = lambda s: print(s, flush=True)  # noqa: E731
     try:
@@ -120,6 +120,7 @@ def main(argv=None):
         sys.exit(f"no decoded_v*_q*_thr*.npy under {args.decoded}")
     L.hip_lib()
     data = load_source(args, m, log)
+    measurer = R.Measurer(ssim=args.ssim)
     os.makedirs(args.output_path, exist_ok=True)
     fps = args.fps or m["fps"]
     done = 0
@@ -144,19 +145,14 @@ def main(argv=None):
                 log(f"{name}: no .y4m: {e}")
         else:
             log(f"{name}: no .y4m: 4:2:0 needs an even width and height, the frames are {W}x{H}")
-        line = f"{name}: {W}x{H}, {tiles} tiles"
+        values, bits = {}, None
         if data is not None:
             if clip >= len(data):
                 sys.exit(f"{name}: the source holds {len(data)} clip(s) of {m['frames']} frames")
-            gt = np.asarray(data[clip], dtype=np.float32) / 255.0
-            line += " PSNR %.3f" % np.mean([cli.cal_psnr(full[t], gt[t]) for t in range(len(full))])
-            if args.ssim:
-                from .ssim import ssim_frames
-                line += " SSIM %.5f" % np.mean(ssim_frames(full, gt[:len(full)]))
+            values = measurer.measure(clip, full, (np.asarray(data[clip], dtype=np.float32) / 255.0)[:len(full)])
         if args.bitstream_dir:
             bits = group_bits(args.bitstream_dir, [clip * tiles + t for t in range(tiles)], q, thr)
-            line += ", %d bits = %.4f bpp (tiles overlap: coded twice)" % (bits, bits / (len(full) * W * H))
-        log(line)
+        log(R.stitcher_line(name, W, H, tiles, values, bits, len(full)))
         done += 1
     log(f"stitched {done} of {len(groups)} group(s) into {args.output_path}")
     if not done:
