@@ -482,9 +482,9 @@ def report_jobs(run, jobs, more=None):
 def run_mask_policy(run, net, models, cfg, data, vids, device, gen):
     """Every clip has the same transmit mask (2 key frames, then generated): decode ``--batch`` clips per launch through the
     receiver (the path bench.py measures) instead of one clip at a time."""
-    from . import sampler as S
+    from . import keystrings as KS, sampler as S
     from .decoder import ClipDecoder, all_generated_mask
-    from .elic import count_bits
+    from .elic import compress_padded, estimate_padded
     args = run.args
     mask = all_generated_mask()
     for q in args.q:
@@ -497,14 +497,11 @@ def run_mask_policy(run, net, models, cfg, data, vids, device, gen):
             keys, shape, est_bits = [], None, []
             key_frames = [] if args.entropy_estimation else None
             for f in (0, 1):                                   # key frames (city_sender.py:521-524), batched
-                pad = (-gt.shape[-1]) % args.patch, (-gt.shape[-2]) % args.patch
-                xk = torch.nn.functional.pad(gt[:, f], (0, pad[0], 0, pad[1]))
-                if args.entropy_estimation:                    # no strings: the decoder is handed the frames themselves
-                    est = model.estimate(xk.to(device))
-                    key_frames.append(est["x_hat"])
-                    est_bits.append((est["bits_y"] + est["bits_z"]).tolist())
+                if args.entropy_estimation:                    # no strings: the decoder is handed the frames themselves, still
+                    xh, b, _ = estimate_padded(model, gt[:, f], args.patch)      # padded, as it decodes the strings' frames
+                    key_frames.append(xh); est_bits.append(b)
                     continue
-                enc = model.compress(xk.to(device))
+                enc = compress_padded(model, gt[:, f], args.patch)     # compress only: ``dec.decode`` below decompresses
                 keys.append(enc["strings"]); shape = enc["shape"]
             d_rx, keys_rx, shape_rx = mask, keys, shape
             if args.bitstream_dir:                             # sender -> file -> receiver
@@ -518,8 +515,8 @@ def run_mask_policy(run, net, models, cfg, data, vids, device, gen):
             frames = dec.decode(d_rx, keys_rx, shape_rx, generator=gen, key_frames=key_frames)[..., :gt.shape[-2], :gt.shape[-1]]
             check_numerics(frames, f"videos {chunk[0]}..{chunk[-1]} q{q}", recovery_note(dec))
             x_all = frames.cpu().numpy()
-            bits = [[b[j] for b in est_bits] if args.entropy_estimation else
-                    [count_bits([[[[p[j]] for p in sl] for sl in k[0]], [k[1][j]]]) for k in keys] for j in range(len(chunk))]
+            per_key = est_bits if args.entropy_estimation else [[KS.bits(s) for s in KS.split(k)] for k in keys]
+            bits = [[b[j] for b in per_key] for j in range(len(chunk))]
             report_jobs(run, [(vid, q, 0.0, x_all[j], gt[j].numpy(), bits[j], mask) for j, vid in enumerate(chunk)])
 
 

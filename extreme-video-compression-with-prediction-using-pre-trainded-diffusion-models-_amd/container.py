@@ -25,10 +25,11 @@ import zlib
 
 import numpy as np
 
+from . import keystrings as KS
+
 MAGIC = b"EVC1"
 FORMAT = 2
 HEADER_BYTES = 4 + 4 + 10          # magic + (format, arith, codec_rev) + 5 x u16
-N_SLICES, N_PASSES = 5, 2
 ARITH_NAMES = {0: "f32", 1: "bf16x6", 2: "f16x3"}
 
 
@@ -45,13 +46,9 @@ def pack(d, key_strings, shape, codec=(1, 1)):
     assert int(d.sum()) == n_key, "mask and key-frame count disagree"
     out = [MAGIC, struct.pack("<BBH", FORMAT, int(codec[0]), int(codec[1])),
            struct.pack("<5H", len(d), n_clips, n_key, int(shape[0]), int(shape[1])), d.tobytes()]
-    for ys, zs in key_strings:
+    for strings in key_strings:
         for b in range(n_clips):
-            out.append(struct.pack("<I", len(zs[b])) + zs[b])
-            for i in range(N_SLICES):
-                for p in range(N_PASSES):
-                    s = ys[i][p][b]
-                    out.append(struct.pack("<I", len(s)) + s)
+            KS.write(out, strings, b)
     return b"".join(out)
 
 
@@ -75,35 +72,12 @@ def unpack(blob, expect_codec=None):
                             "the entropy parameters would differ in the last bit and the range decoder would "
                             "desynchronise (set EVC_CONV_ARITH to match the sender)")
     frames, n_clips, n_key, sh, sw = struct.unpack_from("<5H", blob, 8)
-    off = HEADER_BYTES
-    d = np.frombuffer(blob, dtype=np.uint8, count=frames, offset=off).astype(np.int64)
-    off += frames
+    d = np.frombuffer(blob, dtype=np.uint8, count=frames, offset=HEADER_BYTES).astype(np.int64)
     if int(d.sum()) != n_key:
         raise ValueError("corrupt container: mask and key-frame count disagree")
-
-    def take():
-        nonlocal off
-        if off + 4 > len(blob):
-            raise ValueError("truncated container")
-        (n,) = struct.unpack_from("<I", blob, off)
-        off += 4
-        if off + n > len(blob):
-            raise ValueError("truncated container")
-        s = bytes(blob[off:off + n])
-        off += n
-        return s
-    key_strings = []
-    for _ in range(n_key):
-        ys = [[[None] * n_clips for _ in range(N_PASSES)] for _ in range(N_SLICES)]
-        zs = [None] * n_clips
-        for b in range(n_clips):
-            zs[b] = take()
-            for i in range(N_SLICES):
-                for p in range(N_PASSES):
-                    ys[i][p][b] = take()
-        key_strings.append([ys, zs])
-    if off != len(blob):
-        raise ValueError("trailing bytes in container")
+    reader = KS.Reader(blob, HEADER_BYTES + frames, "container")
+    key_strings = [KS.read(reader, n_clips) for _ in range(n_key)]
+    reader.end()
     return d, key_strings, (sh, sw)
 
 
@@ -198,12 +172,9 @@ def pack_job(segments, key_strings, shape, codec, seed, stream_id, vid, q, thr, 
     if plan is not None:
         out.append(struct.pack(_PLAN_HEAD, int(plan[0]), int(plan[1]), int(crc) & 0xFFFFFFFF))
     out += [struct.pack("<BB", SEGMENT_KINDS.index(k), n) for k, n in segments]
-    for ys, zs in key_strings:
-        assert len(zs) == 1, "a job stream holds one clip"
-        out.append(struct.pack("<I", len(zs[0])) + zs[0])
-        for i in range(N_SLICES):
-            for p in range(N_PASSES):
-                out.append(struct.pack("<I", len(ys[i][p][0])) + ys[i][p][0])
+    for strings in key_strings:
+        assert len(strings[1]) == 1, "a job stream holds one clip"
+        KS.write(out, strings)
     return b"".join(out)
 
 
@@ -224,12 +195,8 @@ def unpack_job(blob, expect_codec=None, expect_plan_revision=None):
         raise CodecMismatch(f"stream was coded with convolution arithmetic {ARITH_NAMES.get(arith, arith)} rev {rev}, this "
                             f"receiver runs {ARITH_NAMES.get(int(expect_codec[0]), expect_codec[0])} rev {int(expect_codec[1])}: "
                             "the entropy parameters would differ in the last bit and the range decoder would desynchronise")
-    off = 8
-    if off + struct.calcsize(_JOB_HEAD) > len(blob):
-        raise ValueError("truncated job stream")
-    (spec, seed, stream_id, vid, q, thr, sampler, subsample, denoise, frames, sh, sw, n_key,
-     n_seg) = struct.unpack_from(_JOB_HEAD, blob, off)
-    off += struct.calcsize(_JOB_HEAD)
+    reader = KS.Reader(blob, 8, "job stream")
+    spec, seed, stream_id, vid, q, thr, sampler, subsample, denoise, frames, sh, sw, n_key, n_seg = reader.unpack(_JOB_HEAD)
     if spec not in NOISE_SPECS:
         raise ValueError(f"unknown noise specification id {spec} (this build replays {sorted(NOISE_SPECS)} = "
                          f"{', '.join(NOISE_SPECS.values())})")
@@ -237,10 +204,7 @@ def unpack_job(blob, expect_codec=None, expect_plan_revision=None):
         raise ValueError(f"corrupt job stream: unknown sampler id {sampler}")
     plan = crc = None
     if fmt == FORMAT_JOB_INVARIANT:
-        if off + struct.calcsize(_PLAN_HEAD) > len(blob):
-            raise ValueError("truncated job stream")
-        plan_id, plan_rev, crc = struct.unpack_from(_PLAN_HEAD, blob, off)
-        off += struct.calcsize(_PLAN_HEAD)
+        plan_id, plan_rev, crc = reader.unpack(_PLAN_HEAD)
         if plan_id not in PLANS:
             raise PlanMismatch(f"unknown generation plan id {plan_id} (this build reproduces {sorted(PLANS)} = "
                                f"{', '.join(PLANS.values())})")
@@ -248,35 +212,16 @@ def unpack_job(blob, expect_codec=None, expect_plan_revision=None):
             raise PlanMismatch(f"stream was generated under revision {plan_rev} of the {PLANS[plan_id]} plan, this receiver's "
                                f"kernels are revision {int(expect_plan_revision)}: its frames would not be the sender's")
         plan = (plan_id, plan_rev)
-    if off + 2 * n_seg > len(blob):
-        raise ValueError("truncated job stream")
+    reader.need(2 * n_seg)
     segments = []
-    for s in range(n_seg):
-        kind, n = struct.unpack_from("<BB", blob, off + 2 * s)
+    for _ in range(n_seg):
+        kind, n = reader.unpack("<BB")
         if kind >= len(SEGMENT_KINDS):
             raise ValueError(f"corrupt job stream: unknown segment kind {kind}")
         segments.append((SEGMENT_KINDS[kind], n))
-    off += 2 * n_seg
     d = check_segments(segments, frames, n_key)
-
-    def take():
-        nonlocal off
-        if off + 4 > len(blob):
-            raise ValueError("truncated job stream")
-        (n,) = struct.unpack_from("<I", blob, off)
-        off += 4
-        if off + n > len(blob):
-            raise ValueError("truncated job stream")
-        s = bytes(blob[off:off + n])
-        off += n
-        return s
-    key_strings = []
-    for _ in range(n_key):
-        zs = [take()]
-        ys = [[[take()] for _ in range(N_PASSES)] for _ in range(N_SLICES)]
-        key_strings.append([ys, zs])
-    if off != len(blob):
-        raise ValueError("trailing bytes in job stream")
+    key_strings = [KS.read(reader) for _ in range(n_key)]
+    reader.end()
     return dict(format=fmt, plan=plan, crc=crc, codec=(arith, rev), noise_spec=spec, seed=seed, stream_id=stream_id, vid=vid, q=q, thr=thr,
                 sampler=SAMPLER_NAMES[sampler], subsample=subsample, denoise=bool(denoise), frames=frames, shape=(sh, sw),
                 segments=segments, d=d, key_strings=key_strings)
@@ -287,5 +232,4 @@ def job_file_name(vid, q, thr):
 
 
 def payload_bits(key_strings):
-    return 8 * sum(len(z) for ys, zs in key_strings for z in zs) + \
-        8 * sum(len(s) for ys, zs in key_strings for sl in ys for ps in sl for s in ps)
+    return KS.bits(key_strings)

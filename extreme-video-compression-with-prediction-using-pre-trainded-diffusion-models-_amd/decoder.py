@@ -13,8 +13,7 @@ must share the same mask (they do in the benchmark pattern; the sender policy ca
 import numpy as np
 import torch
 
-from . import lib as L
-from .elic import count_bits
+from . import keystrings as KS, lib as L, policy as P
 from .recovery import generate_with_recovery, recovery_mode, supports_recovery
 
 
@@ -200,10 +199,7 @@ class ClipDecoder:
                     k += run
                     t += run
                     continue
-                ys = [[[s for f in range(run) for s in key_strings[k + f][0][i][p]] for p in range(2)]
-                      for i in range(len(key_strings[k][0]))]
-                zs = [s for f in range(run) for s in key_strings[k + f][1]]
-                x_hat = self.elic.decompress([ys, zs], shape)["x_hat"]                  # (run*B, 3, H, W)
+                x_hat = self.elic.decompress(KS.merge(key_strings[k:k + run]), shape)["x_hat"]      # (run*B, 3, H, W)
                 B = x_hat.shape[0] // run
                 x_hat = x_hat.reshape(run, B, *x_hat.shape[1:]).permute(1, 0, 2, 3, 4)
                 out.append(x_hat)
@@ -247,117 +243,136 @@ class ClipDecoder:
         either way.  ``stats``: optional dict; ``launch_sizes`` {samples in a launch: launches}, ``samples`` (generated samples),
         ``job_rounds`` (generation segments executed) and ``key_frames_decoded`` are added up in it.
         Returns one (frames, 3, H, W) float32 device tensor per job."""
+        run = _JobRounds(self, jobs, max_batch, models, size, share, stats)
+        run.check_jobs()
+        while True:
+            todo = [j for j in run.jobs if j.pos < len(j.stream["segments"])]
+            if not todo:
+                break
+            run.generation_round([j for j in todo if j.segment[0] == "gen"])
+            run.key_round([j for j in todo if j.segment[0] == "key"])
+            for j in todo:
+                j.pos += 1
+        return [torch.stack(j.x, 0).contiguous() for j in run.jobs]
+
+
+class _RxJob:
+    """One job stream (a ``container.unpack_job`` dict) while ``decode_jobs`` executes it: its decoded frames ``x``, under ``share``
+    their identities ``ids`` (("key", q, n) for the n-th distinct key frame, ``policy.gen_id``), the next segment ``pos`` and the
+    number of key frames consumed ``used``."""
+
+    def __init__(self, stream):
+        self.stream, self.x, self.ids, self.pos, self.used = stream, [], [], 0, 0
+
+    @property
+    def segment(self):
+        return self.stream["segments"][self.pos]
+
+    def segment_strings(self):
+        """Per frame of the key segment in execution, its strings."""
+        return self.stream["key_strings"][self.used:self.used + self.segment[1]]
+
+    def take_keys(self, frames, names=()):
+        """The key segment is done: its frames and, under ``share``, their identities."""
+        self.x, self.ids, self.used = self.x + frames, self.ids + list(names), self.used + len(frames)
+
+
+class _JobRounds:
+    """The steps of one ``ClipDecoder.decode_jobs`` call and what they share."""
+
+    def __init__(self, decoder, streams, max_batch, models, size, share, stats):
+        cfg = decoder.config
+        self.decoder, self.max_batch, self.share, self.stats = decoder, max_batch, share, stats
+        self.jobs = [_RxJob(s) for s in streams]
+        self.size = size if size is not None else (cfg.data.image_size, cfg.data.image_size)
+        self.channels = cfg.data.channels * cfg.data.num_frames
+        self.model_of = (lambda q: decoder.elic) if models is None else (lambda q: models[q])
+        self.grouper, self.key_names = P.StateGrouper(), {}
+
+    def count(self, name, n):
+        if self.stats is not None:
+            self.stats[name] = self.stats.get(name, 0) + n
+
+    def check_jobs(self):
+        """Every stream is one this decoder can replay: known noise, the generator settings it was built with, a sound program."""
         from . import container as Cn, sampler as S
-        cfg = self.config
+        cfg = self.decoder.config
         mine = (getattr(cfg.sampling, "subsample", None) or 0, bool(cfg.sampling.denoise))
-        for job in jobs:
+        for job in (j.stream for j in self.jobs):
             if job["noise_spec"] != Cn.NOISE_N1:
                 raise ValueError(f"unknown noise specification id {job['noise_spec']}")
-            if S.get_sampler(job["sampler"]) is not self.sampler or (job["subsample"], job["denoise"]) != mine:
+            if S.get_sampler(job["sampler"]) is not self.decoder.sampler or (job["subsample"], job["denoise"]) != mine:
                 raise ValueError(f"job stream v{job['vid']} q{job['q']} thr {job['thr']:.2f} was generated with "
                                  f"{job['sampler']}-{job['subsample']} denoise={job['denoise']}: build the decoder with them")
             Cn.check_segments(job["segments"], job["frames"], len(job["key_strings"]))
-        H, W = size if size is not None else (cfg.data.image_size, cfg.data.image_size)
-        model_of = (lambda q: self.elic) if models is None else (lambda q: models[q])
-        ch = cfg.data.channels * cfg.data.num_frames
-        x = [[] for _ in jobs]             # decoded frames per job
-        ids = [[] for _ in jobs]           # share: their identities, ("key", q, n) for the n-th distinct key string, ("gen", serial, t)
-        pos = [0] * len(jobs)              # next segment
-        used = [0] * len(jobs)             # key frames consumed
-        key_names, serial = {}, 0
 
-        def key_name(q, strings):          # (q, string bytes) -> a small id; the bytes are kept once
-            flat = (q,) + tuple(s for sl in strings[0] for p in sl for s in p) + tuple(strings[1])
-            return ("key", q, key_names.setdefault(flat, len(key_names)))
+    def generation_round(self, gen):
+        """gen: the jobs whose segment is ("gen", n).  One seed per noise launch, one generation plan per score-network launch;
+        within those one sample per state (``share``; else per job), ``max_batch`` samples per launch."""
+        launch_of = lambda j: (j.stream["seed"], j.stream.get("plan") is not None)      # noqa: E731
+        for seed, inv in sorted({launch_of(j) for j in gen}):
+            same = [j for j in gen if launch_of(j) == (seed, inv)]
+            states = self.grouper.group(same, self.share, state=lambda j: (j.stream["stream_id"], len(j.x), j.ids[-1], j.ids[-2]))
+            self.count("job_rounds", len(same))
+            self.count("samples", len(states))
+            for c0 in range(0, len(states), self.max_batch):
+                part = states[c0:c0 + self.max_batch]
+                heads = [members[0] for _, members in part]                              # a state's members hold the same frames
+                cond = torch.stack([torch.stack(j.x[-2:], 0) for j in heads], 0).contiguous()
+                noise = P.n1_noise([(j.stream["stream_id"], len(j.x)) for j in heads], seed, self.decoder.device)
+                pred = self.decoder.generate(cond, groups=1, invariant=inv, noise_fn=noise)
+                assert pred.shape[1] * pred.shape[2] == self.channels
+                P.count_launch(self.stats, len(part))
+                for k, (serial, members) in enumerate(part):
+                    for j in members:                                                    # each keeps what its own segment names
+                        n = j.segment[1]
+                        j.x += [pred[k, t] for t in range(n)]
+                        j.ids += [P.gen_id(serial, t) for t in range(n)]
 
-        def count(name, n):
-            if stats is not None:
-                stats[name] = stats.get(name, 0) + n
-        while True:
-            todo = [i for i, job in enumerate(jobs) if pos[i] < len(job["segments"])]
-            if not todo:
-                break
-            gen = [i for i in todo if jobs[i]["segments"][pos[i]][0] == "gen"]
-            key = [i for i in todo if jobs[i]["segments"][pos[i]][0] == "key"]
-            # one seed per noise launch, one generation plan per score-network launch
-            for seed, inv in sorted({(jobs[i]["seed"], jobs[i].get("plan") is not None) for i in gen}):
-                same = [i for i in gen if jobs[i]["seed"] == seed and (jobs[i].get("plan") is not None) == inv]
-                states, at = [], {}                 # a state: the jobs that generate the same chunk; alone unless ``share``
-                for i in same:
-                    k = (jobs[i]["stream_id"], len(x[i]), ids[i][-1], ids[i][-2]) if share else i
-                    if k not in at:
-                        at[k] = len(states)
-                        states.append([])
-                    states[at[k]].append(i)
-                count("job_rounds", len(same))
-                count("samples", len(states))
-                for c0 in range(0, len(states), max_batch):
-                    part = states[c0:c0 + max_batch]
-                    heads = [members[0] for members in part]
-                    cond = torch.stack([torch.stack(x[i][-2:], 0) for i in heads], 0).contiguous()
-                    keys = L.noise_keys([(jobs[i]["stream_id"], len(x[i])) for i in heads], self.device)
-                    pred = self.generate(cond, groups=1, invariant=inv, noise_fn=lambda tag, shape, keys=keys, seed=seed: L.noise_normal(
-                        keys, shape, seed, 0 if tag == "init" else int(tag) + 1))
-                    assert pred.shape[1] * pred.shape[2] == ch
-                    if stats is not None:
-                        h = stats.setdefault("launch_sizes", {})
-                        h[len(part)] = h.get(len(part), 0) + 1
-                    for k, members in enumerate(part):
-                        for i in members:
-                            n_i = jobs[i]["segments"][pos[i]][1]
-                            x[i] += [pred[k, t] for t in range(n_i)]
-                            ids[i] += [("gen", serial, t) for t in range(n_i)]
-                        serial += 1
-            for q in sorted({jobs[i]["q"] for i in key}):
-                same = [i for i in key if jobs[i]["q"] == q]
-                if share:                  # every distinct key frame of the round once, then handed to the jobs that name it
-                    want, order = {}, []
-                    for i in same:
-                        for f in range(jobs[i]["segments"][pos[i]][1]):
-                            name = key_name(q, jobs[i]["key_strings"][used[i] + f])
-                            if name not in want:
-                                want[name] = jobs[i]["key_strings"][used[i] + f]
-                                order.append(name)
-                    shape = jobs[same[0]]["shape"]
-                    assert all(tuple(jobs[i]["shape"]) == tuple(shape) for i in same), "one frame size per decoder"
-                    frame_of = {}
-                    for c0 in range(0, len(order), max_batch):
-                        ks = [want[name] for name in order[c0:c0 + max_batch]]
-                        ys = [[[s for k_ in ks for s in k_[0][sl][p]] for p in range(2)] for sl in range(len(ks[0][0]))]
-                        zs = [s for k_ in ks for s in k_[1]]
-                        x_hat = model_of(q).decompress([ys, zs], shape)["x_hat"][:, :, :H, :W]
-                        for o, name in enumerate(order[c0:c0 + max_batch]):
-                            frame_of[name] = x_hat[o]
-                    count("key_frames_decoded", len(order))
-                    for i in same:
-                        n_i = jobs[i]["segments"][pos[i]][1]
-                        names = [key_name(q, jobs[i]["key_strings"][used[i] + f]) for f in range(n_i)]
-                        x[i] += [frame_of[name] for name in names]
-                        ids[i] += names
-                        used[i] += n_i
-                    same = []
-                while same:
-                    part, n = [], 0
-                    while same and (not part or n + jobs[same[0]]["segments"][pos[same[0]]][1] <= max_batch):
-                        n += jobs[same[0]]["segments"][pos[same[0]]][1]
-                        part.append(same.pop(0))
-                    shape = jobs[part[0]]["shape"]
-                    assert all(tuple(jobs[i]["shape"]) == tuple(shape) for i in part), "one frame size per decoder"
-                    ks = [jobs[i]["key_strings"][used[i] + f] for i in part for f in range(jobs[i]["segments"][pos[i]][1])]
-                    ys = [[[s for k_ in ks for s in k_[0][sl][p]] for p in range(2)] for sl in range(len(ks[0][0]))]
-                    zs = [s for k_ in ks for s in k_[1]]
-                    x_hat = model_of(q).decompress([ys, zs], shape)["x_hat"][:, :, :H, :W]
-                    o = 0
-                    count("key_frames_decoded", len(ks))
-                    for i in part:
-                        n_i = jobs[i]["segments"][pos[i]][1]
-                        x[i] += [x_hat[o + f] for f in range(n_i)]
-                        o += n_i
-                        used[i] += n_i
-            for i in todo:
-                pos[i] += 1
-        return [torch.stack(f, 0).contiguous() for f in x]
+    def decode_keys(self, q, strings, jobs):
+        """strings: per frame, in launch order, of key frames of ``jobs`` -> the frames of one ``decompress`` call of q's model,
+        cropped to the frame size as the sender crops its padded frames."""
+        shape = jobs[0].stream["shape"]
+        assert all(tuple(j.stream["shape"]) == tuple(shape) for j in jobs), "one frame size per decoder"
+        H, W = self.size
+        return self.model_of(q).decompress(KS.merge(strings), shape)["x_hat"][:, :, :H, :W]
+
+    def key_name(self, q, strings):
+        """(q, string bytes) -> a small id; the bytes are kept once."""
+        return ("key", q, self.key_names.setdefault((q,) + KS.flat(strings), len(self.key_names)))
+
+    def key_round(self, key):
+        """key: the jobs whose segment is ("key", n): per q, ``shared_keys`` or ``segment_keys``."""
+        for q in sorted({j.stream["q"] for j in key}):
+            (self.shared_keys if self.share else self.segment_keys)(q, [j for j in key if j.stream["q"] == q])
+
+    def shared_keys(self, q, same):
+        """Every distinct key frame of the round once, in first-seen order, ``max_batch`` per call, for the jobs that name it."""
+        names = [[self.key_name(q, s) for s in j.segment_strings()] for j in same]
+        want = {}
+        for j, mine in zip(same, names):
+            for name, s in zip(mine, j.segment_strings()):
+                want.setdefault(name, s)
+        order, frame_of = list(want), {}
+        for c0 in range(0, len(order), self.max_batch):
+            part = order[c0:c0 + self.max_batch]
+            frame_of.update(zip(part, self.decode_keys(q, [want[name] for name in part], same)))
+        self.count("key_frames_decoded", len(order))
+        for j, mine in zip(same, names):
+            j.take_keys([frame_of[name] for name in mine], mine)
+
+    def segment_keys(self, q, same):
+        """Whole segments in job order, packed greedily up to ``max_batch`` frames per call: a segment is never split."""
+        while same:
+            part, n = [], 0
+            while same and (not part or n + same[0].segment[1] <= self.max_batch):
+                n += same[0].segment[1]
+                part.append(same.pop(0))
+            x_hat = iter(self.decode_keys(q, [s for j in part for s in j.segment_strings()], part))
+            self.count("key_frames_decoded", n)
+            for j in part:
+                j.take_keys([next(x_hat) for _ in range(j.segment[1])])
 
 
 def total_bits(key_strings):
-    return sum(count_bits(s) for s in key_strings)
+    return KS.bits(key_strings)

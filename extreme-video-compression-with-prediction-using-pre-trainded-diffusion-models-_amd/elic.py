@@ -22,7 +22,7 @@ Every convolution runs through ``evc_conv2d_nhwc_f32`` (NHWC, f32 matrix cores):
 import numpy as np
 import torch
 
-from . import lib as L
+from . import keystrings as KS, lib as L
 from .entropy import (DensityParametersMissing, EntropyBottleneckCodec, Tables, density_from_state_dict, pack_density)
 
 GROUPS = [0, 16, 16, 32, 64, 192]   # Network.py:87
@@ -319,37 +319,56 @@ class ElicModel:
 
 def count_bits(strings):
     """Inference.py:51-67: 8 x total byte length of the nested [y_strings, z_strings] lists."""
-    total = 0
-    for s in strings:
-        for j in s:
-            if isinstance(j, list):
-                for i in j:
-                    total += sum(len(k) for k in i) if isinstance(i, list) else len(i)
-            else:
-                total += len(j)
-    return 8 * total
+    return KS.bits(strings)
+
+
+def pad_to_patch(x, patch):
+    """(n, 3, H, W) -> zero-padded at the bottom and the right to multiples of ``patch`` (Inference.py:30-37)."""
+    h, w = x.shape[-2:]
+    return torch.nn.functional.pad(x, (0, (-w) % patch, 0, (-h) % patch))
+
+
+def compress_padded(model, x, patch):
+    """The sender's half of ``coded_batch``: ``compress`` of the padded frames -> {"strings" of the batch, "shape"}."""
+    return model.compress(pad_to_patch(x, patch))
+
+
+def estimate_padded(model, x, patch):
+    """``estimate`` of the padded frames -> (x_hat still padded, bits[n] as Python floats, shape); one read-back per call."""
+    est = model.estimate(pad_to_patch(x, patch))
+    return est["x_hat"], (est["bits_y"] + est["bits_z"]).tolist(), est["shape"]
+
+
+def coded_batch(model, x, patch=64):
+    """Inference.inference (Inference.py:19-75) for a batch that also keeps what a receiver needs: x (n, 3, H, W) in [0, 1] ->
+    (x_hat (n, 3, H, W), bits[n], strings[n], shape), strings[b] = ``[y_strings[5][2][1], z_strings[1]]`` of frame b alone (the
+    per-key-frame entry of a job stream, container.pack_job)."""
+    h, w = x.shape[-2:]
+    enc = compress_padded(model, x, patch)
+    strings = KS.split(enc["strings"])
+    x_hat = model.decompress(enc["strings"], enc["shape"])["x_hat"][:, :, :h, :w]
+    return x_hat, [KS.bits(s) for s in strings], strings, enc["shape"]
+
+
+def estimated_batch(model, x, patch=64):
+    """``coded_batch`` under --entropy-estimation: -> (x_hat, bits[n] as Python floats, None, shape).  The frames are those of
+    ``coded_batch`` bit for bit; the bits are the sums of -log2(likelihood) of ``ElicModel.estimate`` (no strings exist, hence
+    None)."""
+    h, w = x.shape[-2:]
+    x_hat, bits, shape = estimate_padded(model, x, patch)
+    return x_hat[:, :, :h, :w], bits, None, shape
 
 
 @torch.no_grad()
 def inference(model, x, patch=64):
     """Inference.inference (Inference.py:19-75): x (3,H,W) in [0,1] -> (x_hat (1,3,H,W), bits)."""
-    x = x.unsqueeze(0)
-    h, w = x.size(2), x.size(3)
-    new_h, new_w = (h + patch - 1) // patch * patch, (w + patch - 1) // patch * patch
-    xp = torch.nn.functional.pad(x, (0, new_w - w, 0, new_h - h))
-    enc = model.compress(xp)
-    dec = model.decompress(enc["strings"], enc["shape"])
-    x_hat = dec["x_hat"][:, :, :h, :w]
-    return x_hat, count_bits(enc["strings"])
+    x_hat, bits, _, _ = coded_batch(model, x.unsqueeze(0), patch)
+    return x_hat, bits[0]
 
 
 @torch.no_grad()
 def inference_estimate(model, x, patch=64):
     """``inference`` under the reference's --entropy-estimation: x (3,H,W) in [0,1] -> (x_hat (1,3,H,W), bits as a float), the
     bits estimated from the likelihoods (``ElicModel.estimate``) instead of counted from coded strings."""
-    x = x.unsqueeze(0)
-    h, w = x.size(2), x.size(3)
-    new_h, new_w = (h + patch - 1) // patch * patch, (w + patch - 1) // patch * patch
-    xp = torch.nn.functional.pad(x, (0, new_w - w, 0, new_h - h))
-    est = model.estimate(xp)
-    return est["x_hat"][:, :, :h, :w], float(est["bits_y"][0] + est["bits_z"][0])
+    x_hat, bits, _, _ = estimated_batch(model, x.unsqueeze(0), patch)
+    return x_hat, bits[0]

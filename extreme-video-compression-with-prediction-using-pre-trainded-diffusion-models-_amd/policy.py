@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .elic import count_bits
+from .elic import coded_batch, estimated_batch  # noqa: F401  (the sweep's key-frame calls; importable from here as before)
 from .report import cal_psnr
 
 
@@ -104,43 +104,6 @@ def load_metric(policy, spec=None, device="cuda", net="alex"):
     return CallableMetric(lambda a, b: net(a, b).reshape(-1), name="lpips-alex")
 
 
-def inference_batch(model, x, patch):
-    """Inference.inference (Inference.py:19-75) for a batch: x (n, 3, H, W) in [0, 1] -> (x_hat (n, 3, H, W), bits[n])."""
-    n, _, h, w = x.shape
-    ph, pw = (-h) % patch, (-w) % patch
-    xp = torch.nn.functional.pad(x, (0, pw, 0, ph))
-    enc = model.compress(xp)
-    dec = model.decompress(enc["strings"], enc["shape"])["x_hat"][:, :, :h, :w]
-    ys, zs = enc["strings"]
-    bits = [count_bits([[[[p[b]] for p in sl] for sl in ys], [zs[b]]]) for b in range(n)]
-    return dec, bits
-
-
-def coded_batch(model, x, patch):
-    """``inference_batch`` that also keeps what a receiver needs: -> (x_hat, bits[n], strings[n], shape), strings[b] =
-    ``[y_strings[5][2][1], z_strings[1]]`` of frame b alone (the per-key-frame entry of a job stream, container.pack_job)."""
-    n, _, h, w = x.shape
-    ph, pw = (-h) % patch, (-w) % patch
-    xp = torch.nn.functional.pad(x, (0, pw, 0, ph))
-    enc = model.compress(xp)
-    dec = model.decompress(enc["strings"], enc["shape"])["x_hat"][:, :, :h, :w]
-    ys, zs = enc["strings"]
-    strings = [[[[[p[b]] for p in sl] for sl in ys], [zs[b]]] for b in range(n)]
-    return dec, [count_bits(s) for s in strings], strings, enc["shape"]
-
-
-def estimated_batch(model, x, patch):
-    """``coded_batch`` under --entropy-estimation: -> (x_hat, bits[n] as Python floats, None, shape).  The frames are those of
-    ``coded_batch`` bit for bit; the bits are the sums of -log2(likelihood) of ``ElicModel.estimate`` (no strings exist, hence
-    None), read back once per call."""
-    h, w = x.shape[-2:]
-    ph, pw = (-h) % patch, (-w) % patch
-    xp = torch.nn.functional.pad(x, (0, pw, 0, ph))
-    est = model.estimate(xp)
-    bits = (est["bits_y"] + est["bits_z"]).tolist()
-    return est["x_hat"][:, :, :h, :w], bits, None, est["shape"]
-
-
 class _Job:
     __slots__ = ("uid", "sid", "vid", "q", "thr", "x", "ids", "d", "bits", "round", "segments", "strings")
 
@@ -179,18 +142,35 @@ class StateGrouper:
     def state_of(job):
         return (job.vid, job.q, len(job.ids), job.ids[-1], job.ids[-2])
 
-    def group(self, jobs, share=True):
-        """jobs: the round's active jobs (``vid``, ``q``, ``ids``) -> [(serial, [member jobs])], states in the order of their
-        first member, members in the order given.  ``share=False``: every job is a state of its own."""
+    def group(self, jobs, share=True, state=None):
+        """jobs: the round's active jobs -> [(serial, [member jobs])], states in the order of their first member, members in the
+        order given.  ``state``: job -> its state, a hashable (default ``state_of``, the sender's: ``vid``, ``q``, ``ids``; the
+        receiver passes its own).  ``share=False``: every job is a state of its own."""
+        state = self.state_of if state is None else state
         states, at = [], {}
         for j in jobs:
-            k = self.state_of(j) if share else id(j)
+            k = state(j) if share else id(j)
             if k not in at:
                 at[k] = len(states)
                 states.append((self.serial, []))
                 self.serial += 1
             states[at[k]][1].append(j)
         return states
+
+
+def n1_noise(pairs, seed, device):
+    """Noise specification N1 for one launch: pairs = per sample (stream id, start frame = frames held when the round starts)
+    -> ``noise_fn(tag, shape)`` of ``ClipDecoder.generate``.  The keys go up once; every step is one launch for the whole batch
+    (step 0 = x_T, step i + 1 = the noise of sampler step i).  Sender and receiver both draw through here."""
+    keys = L.noise_keys(pairs, device)
+    return lambda tag, shape: L.noise_normal(keys, shape, seed, 0 if tag == "init" else int(tag) + 1)
+
+
+def count_launch(stats, samples):
+    """One generation launch more in ``stats["launch_sizes"]`` = {samples in a launch: launches} (``stats`` may be None)."""
+    if stats is not None:
+        h = stats.setdefault("launch_sizes", {})
+        h[samples] = h.get(samples, 0) + 1
 
 
 def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=30, max_batch=32, seed=0,
@@ -297,9 +277,8 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
         add_keys(j, (0, 1))
 
     def _noise_for(batch):
-        if noise == "evc" and noise_source is None:      # the round's keys go up once; one launch per step for the whole batch
-            keys = L.noise_keys([(j.sid, len(j.x)) for j in batch], device)
-            return lambda tag, shape: L.noise_normal(keys, shape, seed, 0 if tag == "init" else int(tag) + 1)
+        if noise == "evc" and noise_source is None:
+            return n1_noise([(j.sid, len(j.x)) for j in batch], seed, device)
 
         def fn(tag, shape):      # one counter-based stream per (job, round, step) -- per (group, start frame, step) under group
             # streams --: independent of the batch composition
@@ -342,9 +321,7 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
             cond = torch.stack([torch.stack(j.x[-2:], 0) for j in batch], 0).contiguous()     # (n, 2, 3, H, W)
             pred = decoder.generate(cond, noise_fn=noise_for(batch), groups=1,              # (n, 5, 3, H, W)
                                     invariant=True if batch_invariant else None)
-            if stats is not None:
-                h = stats.setdefault("launch_sizes", {})
-                h[len(batch)] = h.get(len(batch), 0) + 1
+            count_launch(stats, len(batch))
             n_new = [min(pred.shape[1], frames - len(j.x)) for j in batch]
             flat_p = torch.cat([pred[k, :n_new[k]] for k in range(len(batch))], 0)
             flat_g = torch.cat([gt_dev[j.vid][len(j.x):len(j.x) + n_new[k]] for k, j in enumerate(batch)], 0)
