@@ -14,7 +14,8 @@ absent.  ``--fvd`` (or ``i3d_pretrained_400.pt`` found where the reference keeps
 reference's third per-job number, the FVD of the decoded clip against the original (city_sender.py:575-589), computed by the
 HIP I3D network (fvd.py) and saved as ``fvd_<idx>.npy``.  Under a decision rule ``--bitstream-dir DIR`` writes one replayable
 job stream per reported job (container format 3; format 4 with ``--batch-invariant``) for ``city_receiver.py`` and runs the sweep on noise specification N1
-(``--noise evc``).  ``--gpus N`` (or ``torch.distributed.run``) block-shards the video range over N ranks, one GPU each.
+(``--noise evc``).  ``--noise-trials K`` draws every generation round K times and keeps, per job, the draw
+that serves it best (``policy.choose_trial``); the job stream names it (formats 5 / 6) and its bits are part of the reported BPP.  ``--gpus N`` (or ``torch.distributed.run``) block-shards the video range over N ranks, one GPU each.
 ``--data_yuv FILE`` reads the clips from a Y4M or raw planar YUV 4:2:0 file instead of ``--data_npy`` (video_io.py: the
 reference's benchmark conventions, converted by the HIP kernels of csrc/yuv.hip), ``--yuv-out`` writes each job's decoded clip
 as ``.y4m`` and ``--yuv-metrics`` adds the PSNR of the reference's codec benchmark.  ``--yuv-fit crop``
@@ -123,6 +124,14 @@ def build_parser():
                         "of the (video, q) pair) and each round generates once per distinct state -- the jobs that hold the "
                         "same last two frames -- instead of once per job (DESIGN.md section 1).  The jobs of one (video, q) "
                         "are then correlated samples; each is still what a receiver decodes from its own stream")
+    p.add_argument("--noise-trials", type=int, default=1, metavar="K",
+                   help="psnr / lpips policy: draw every generation round K times (noise trial t keys specification N1 with start "
+                        "frame + 65536 t; trial 0 is the plain key), keep per job the draw whose accepted prefix is longest "
+                        "(ties: the better mean metric, then the lowest trial) and name it in the job stream for ceil(log2 K) "
+                        "bits per generated segment, which BPP includes (DESIGN.md sections 1 and 5).  The sender generates K "
+                        "times as much; the receiver generates the chosen draw only.  Needs the replayable noise (--noise evc, "
+                        "selected when --noise is not given); --policy psnr then sums the squared error on the GPU "
+                        "(csrc/metric.hip); job streams are container formats 5 / 6.  1 <= K <= 255, K <= --policy-batch")
     p.add_argument("--range-recovery", choices=["off", "layer"], default=None,
                    help="layer: when a chunk raises an fp16-split range event, demote only the layers that raised it to the "
                         "bf16x6 split and regenerate the chunk with the same noise (default: EVC_RANGE_RECOVERY, else off: "
@@ -158,7 +167,7 @@ def build_parser():
 
 YUV_FLAGS = ("data_yuv", "yuv_geometry", "yuv_upsample", "yuv_out", "yuv_metrics", "yuv_fit", "yuv_resize", "data_frames",
              "yuv_tile_overlap")
-OPT_IN_FLAGS = YUV_FLAGS + ("ssim", "lpips", "lpips_net", "fid", "fid_dims")       # written to args.yml only when used: a run without them leaves what it always left
+OPT_IN_FLAGS = YUV_FLAGS + ("ssim", "lpips", "lpips_net", "fid", "fid_dims", "noise_trials")       # written to args.yml only when used: a run without them leaves what it always left
 
 
 def add_yuv_input_flags(p):
@@ -405,6 +414,21 @@ def resolve_noise(args, say):
         if args.noise is None:
             say("noise: evc (specification N1) because --batch-invariant frames are meant to be reproduced")
             args.noise = "evc"
+    if args.noise_trials != 1:
+        if not 1 <= args.noise_trials <= 255:
+            sys.exit(f"--noise-trials {args.noise_trials}: 1 .. 255 (a job stream names the trial in one byte)")
+        if args.policy == "mask":
+            sys.exit("--noise-trials applies to the psnr / lpips policy sweep (the mask policy judges nothing, so there is no "
+                     "draw to prefer)")
+        if args.noise == "torch":
+            sys.exit("--noise-trials with --noise torch: the receiver regenerates the chosen draw from its trial number, which "
+                     "only the keyed noise of specification N1 allows; drop --noise or pass --noise evc")
+        if args.noise_trials > args.policy_batch:
+            sys.exit(f"--noise-trials {args.noise_trials} > --policy-batch {args.policy_batch}: the trials of a state ride in "
+                     "one launch, and --policy-batch counts samples")
+        if args.noise is None:
+            say("noise: evc (specification N1) because --noise-trials names its draws by their key")
+            args.noise = "evc"
     if args.share_generations and args.policy == "mask":
         sys.exit("--share-generations applies to the psnr / lpips policy sweep (the mask policy has one job per clip)")
     if args.policy != "mask":
@@ -461,14 +485,18 @@ def load_data(args, cfg, rank, log):
     sys.exit(f"missing {args.data_npy} (pass --synthetic)")
 
 
-def report_jobs(run, jobs, more=None):
+def report_jobs(run, jobs, more=None, trials=None):
     """jobs: [(vid, q, thr, x, gt, bits, d)] that passed ``check_numerics``, x and gt numpy (30, 3, H, W).  They are measured
     together (report.Measurer: one I3D pass for the call's clips); then, job by job, the lines are printed, city_output_npy /
-    .png / .y4m written and the values handed to the collector.  more: per job, values measured elsewhere."""
+    .png / .y4m written and the values handed to the collector.  more: per job, values measured elsewhere.  trials: per job of
+    a --noise-trials sweep, (K, trial bits): the bits join the job's BPP and its first line says so."""
     values = run.measurer.measure_jobs([(vid, x, gt) for vid, _, _, x, gt, _, _ in jobs])
-    for (vid, q, thr, x, gt, bits, d), v, extra in zip(jobs, values, more or [{}] * len(jobs)):
-        bpp = sum(bits) / 128 / 128 / 30
-        for line in R.sender_lines(v, d, bpp, run.measurer.net):
+    for i, ((vid, q, thr, x, gt, bits, d), v, extra) in enumerate(zip(jobs, values, more or [{}] * len(jobs))):
+        bpp = (sum(bits) if trials is None else sum(bits) + trials[i][1]) / 128 / 128 / 30
+        lines = R.sender_lines(v, d, bpp, run.measurer.net)
+        if trials is not None:
+            lines[0] += f" trials {trials[i][0]} (+{trials[i][1]} bits)"
+        for line in lines:
             run.log(f"video {vid} q{q} thr {thr:.2f}: {line}")
         out = os.path.join(run.args.output_path, f"output_{vid}")
         save_output(np.concatenate(list(gt.transpose(0, 2, 3, 1)), axis=1), np.concatenate(list(x.transpose(0, 2, 3, 1)), axis=1),
@@ -531,13 +559,17 @@ def run_policy_sweep(run, net, models, cfg, data, vids, device):
     else:
         thresholds = args.thresholds or [0.0]
     metric = P.load_metric(args.policy, args.metric, device, net=args.lpips_net)
+    if args.noise_trials > 1 and args.policy == "psnr":
+        metric = P.PsnrDeviceMetric()        # K times the candidates: their squared error is summed where they are
     dec = ClipDecoder(net, None, cfg, S.get_sampler(args.sampler), range_recovery=args.range_recovery, log=run.log)
     clips = {vid: torch.from_numpy(np.asarray(data[vid], dtype=np.float32) / 255.0) for vid in vids}
     shared = dict(noise_streams="group", share=True, stats={}) if args.share_generations else {}
+    if args.noise_trials > 1:
+        shared["trials"] = args.noise_trials
     res = P.run_policy(dec, models, clips, args.q, thresholds, metric, patch=args.patch, max_batch=args.policy_batch,
                        seed=args.seed, device=device, bpp_limit=args.bpp_limit, log=run.log,
                        noise=args.noise, batch_invariant=args.batch_invariant, estimate=args.entropy_estimation, **shared)
-    if shared:
+    if args.share_generations:
         st = shared["stats"]
         run.log(f"shared generations: {sum(st['states'])} sample-rounds generated for {sum(st['jobs_served'])} "
                 f"job-rounds served ({len(st['states'])} rounds)")
@@ -553,7 +585,8 @@ def run_policy_sweep(run, net, models, cfg, data, vids, device):
             if args.policy == "lpips":      # per-frame distances of the decoded clip (city_sender.py:570-571)
                 more = [{"policy_lpips": metric.values(torch.from_numpy(r["x"]).to(device), clips[vid].to(device))}
                         for r in res[(vid, q)]]
-            report_jobs(run, [(vid, q, r["thr"], r["x"], clips[vid].numpy(), r["bits"], r["d"]) for r in res[(vid, q)]], more)
+            trials = [(r["n_trials"], r["trial_bits"]) for r in res[(vid, q)]] if args.noise_trials > 1 else None
+            report_jobs(run, [(vid, q, r["thr"], r["x"], clips[vid].numpy(), r["bits"], r["d"]) for r in res[(vid, q)]], more, trials)
 
 
 def main(argv=None):

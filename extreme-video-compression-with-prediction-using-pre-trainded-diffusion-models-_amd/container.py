@@ -19,6 +19,7 @@ The payload bytes are exactly the strings the codec produced, so ``8 * payload``
 Format 3 (``pack_job`` / ``unpack_job``, further down) is the stream of ONE policy job: its program of key / generated
 segments and the key of its noise, so that a receiver replays exactly what the sender judged.  Format 4 is format 3 for a
 job generated in batch-invariant mode: it adds the generation plan (id, revision) and a CRC-32 of the sender's frames.
+Formats 5 and 6 are formats 3 and 4 of a sweep with noise trials: every generated segment names the draw the sender kept.
 """
 import struct
 import zlib
@@ -107,8 +108,21 @@ def unpack(blob, expect_codec=None):
 # of invariant mode); the CRC is ``zlib.crc32`` of the job's decoded frames (frames, 3, H, W) as C-contiguous float32 bytes.
 # A receiver refuses an unknown plan id, or another revision (``PlanMismatch``), as it refuses a foreign codec tag.  Jobs
 # generated in the default mode keep writing format 3, byte for byte.
+#
+# Formats 5 and 6 = formats 3 and 4 for a job of a sweep with NOISE TRIALS (policy.run_policy(trials=K), K > 1): the sender drew
+# every round K times and kept the draw that served it best, so each generated segment names its trial.  Two changes:
+#
+#                  | u8 n_trials (K, >= 2)           directly after the head (format 6: after the plan head)
+#                  | n_segments x (u8 kind | u8 n | u8 trial)
+#
+# A ("gen", n) segment of trial t draws the key (seed, stream id, start frame + 65536 t, step): trial 0 is the key of formats
+# 3 / 4, and the noise specification id stays 1.  A key segment's trial is 0 and a trial is < n_trials; anything else is a
+# corrupt stream.  Jobs of a sweep without trials keep writing formats 3 / 4, byte for byte.
 FORMAT_JOB = 3
 FORMAT_JOB_INVARIANT = 4
+FORMAT_JOB_TRIALS = 5
+FORMAT_JOB_INVARIANT_TRIALS = 6
+JOB_FORMATS = (FORMAT_JOB, FORMAT_JOB_INVARIANT, FORMAT_JOB_TRIALS, FORMAT_JOB_INVARIANT_TRIALS)
 PLAN_INVARIANT = 1
 PLANS = {PLAN_INVARIANT: "batch-invariant"}
 _PLAN_HEAD = "<BHI"                # plan id, plan revision, frames CRC-32
@@ -153,11 +167,26 @@ def check_segments(segments, frames, n_key=None):
     return np.asarray(d, dtype=np.int64)
 
 
+def check_trials(segments, trials, n_trials):
+    """The rules of the trial numbers of a format-5 / format-6 program; raises ValueError."""
+    if not 2 <= n_trials <= 255:
+        raise ValueError(f"corrupt job stream: a stream with noise trials names 2..255 of them, not {n_trials}")
+    if len(trials) != len(segments):
+        raise ValueError(f"corrupt job stream: {len(trials)} trial numbers for {len(segments)} segments")
+    for (kind, _), t in zip(segments, trials):
+        if kind == "key" and t != 0:
+            raise ValueError(f"corrupt job stream: a key segment with noise trial {t}")
+        if not 0 <= t < n_trials:
+            raise ValueError(f"corrupt job stream: noise trial {t} of {n_trials}")
+
+
 def pack_job(segments, key_strings, shape, codec, seed, stream_id, vid, q, thr, sampler, subsample, denoise,
-             noise_spec=NOISE_N1, plan=None, crc=None):
+             noise_spec=NOISE_N1, plan=None, crc=None, trials=None, n_trials=1):
     """One policy job -> bytes.  ``plan`` = (plan id, plan revision) and ``crc`` = ``frames_crc`` of the sender's frames make it
     a format-4 stream (a job generated in batch-invariant mode); without them it is format 3.  segments: [("key" | "gen", n)]; key_strings: per key frame, in order, ``[y_strings[5][2][1],
-    z_strings[1]]`` (one clip); codec: ``ElicModel.codec_tag()`` of the encoder; sampler: "DDPM" | "DDIM" | "FPNDM"."""
+    z_strings[1]]`` (one clip); codec: ``ElicModel.codec_tag()`` of the encoder; sampler: "DDPM" | "DDIM" | "FPNDM".
+    ``n_trials`` > 1 with ``trials`` (per segment: 0 for key, the chosen noise trial for gen) makes it format 5 (6 with a plan);
+    ``n_trials`` = 1 writes formats 3 / 4 and takes no trial but 0."""
     segments = [(str(k), int(n)) for k, n in segments]
     frames = sum(n for _, n in segments)
     check_segments(segments, frames, len(key_strings))
@@ -165,13 +194,24 @@ def pack_job(segments, key_strings, shape, codec, seed, stream_id, vid, q, thr, 
         raise ValueError("a format-4 job stream needs both its generation plan and the CRC of the sender's frames")
     if plan is not None and int(plan[0]) not in PLANS:
         raise ValueError(f"unknown generation plan id {plan[0]}")
-    out = [MAGIC, struct.pack("<BBH", FORMAT_JOB if plan is None else FORMAT_JOB_INVARIANT, int(codec[0]), int(codec[1])),
+    n_trials = int(n_trials)
+    trials = [0] * len(segments) if trials is None else [int(t) for t in trials]
+    if n_trials > 1:
+        check_trials(segments, trials, n_trials)
+    elif n_trials != 1 or any(trials):
+        raise ValueError(f"a job stream without noise trials (n_trials = {n_trials}) names no trial but 0")
+    fmt = (FORMAT_JOB, FORMAT_JOB_INVARIANT, FORMAT_JOB_TRIALS, FORMAT_JOB_INVARIANT_TRIALS)[2 * (n_trials > 1) + (plan is not None)]
+    out = [MAGIC, struct.pack("<BBH", fmt, int(codec[0]), int(codec[1])),
            struct.pack(_JOB_HEAD, int(noise_spec), int(seed) & (2 ** 64 - 1), int(stream_id), int(vid), int(q), float(thr),
                        SAMPLER_IDS[sampler], int(subsample), int(bool(denoise)), frames, int(shape[0]), int(shape[1]),
                        len(key_strings), len(segments))]
     if plan is not None:
         out.append(struct.pack(_PLAN_HEAD, int(plan[0]), int(plan[1]), int(crc) & 0xFFFFFFFF))
-    out += [struct.pack("<BB", SEGMENT_KINDS.index(k), n) for k, n in segments]
+    if n_trials > 1:
+        out.append(struct.pack("<B", n_trials))
+        out += [struct.pack("<BBB", SEGMENT_KINDS.index(k), n, t) for (k, n), t in zip(segments, trials)]
+    else:
+        out += [struct.pack("<BB", SEGMENT_KINDS.index(k), n) for k, n in segments]
     for strings in key_strings:
         assert len(strings[1]) == 1, "a job stream holds one clip"
         KS.write(out, strings)
@@ -180,17 +220,21 @@ def pack_job(segments, key_strings, shape, codec, seed, stream_id, vid, q, thr, 
 
 def unpack_job(blob, expect_codec=None, expect_plan_revision=None):
     """bytes of ``pack_job`` -> dict(format, codec, noise_spec, seed, stream_id, vid, q, thr, sampler, subsample, denoise,
-    frames, shape, segments, d, key_strings, plan, crc); ``plan`` = (id, revision) and ``crc`` of a format-4 stream, None for
-    format 3.  Raises ValueError for anything but a complete, consistent format-3 / format-4 stream of a known noise
+    frames, shape, segments, d, key_strings, plan, crc, trials, n_trials); ``plan`` = (id, revision) and ``crc`` of a format-4 /
+    format-6 stream, None for formats 3 / 5; ``segments`` are (kind, n) pairs in every format, ``trials`` the noise trial per
+    segment and ``n_trials`` the sender's K (all 0 and 1 for formats 3 / 4).  Raises ValueError for anything but a complete,
+    consistent job stream (formats 3 .. 6) of a known noise
     specification and generation plan, ``CodecMismatch`` for a stream coded under another arithmetic / kernel revision,
     ``PlanMismatch`` for a format-4 stream of another plan revision than ``expect_plan_revision`` (the receiver's
     ``lib.invariant_plan_revision()``; None = not checked)."""
     if blob[:4] != MAGIC or len(blob) < 8:
         raise ValueError("not an EVC1 container")
     fmt, arith, rev = struct.unpack_from("<BBH", blob, 4)
-    if fmt not in (FORMAT_JOB, FORMAT_JOB_INVARIANT):
-        raise ValueError(f"not a job stream: EVC1 container format {fmt} (job streams are formats {FORMAT_JOB} and "
-                         f"{FORMAT_JOB_INVARIANT})")
+    if fmt not in JOB_FORMATS:
+        raise ValueError(f"not a job stream: EVC1 container format {fmt} (job streams are formats "
+                         f"{', '.join(str(f) for f in JOB_FORMATS)})")
+    invariant = fmt in (FORMAT_JOB_INVARIANT, FORMAT_JOB_INVARIANT_TRIALS)
+    with_trials = fmt in (FORMAT_JOB_TRIALS, FORMAT_JOB_INVARIANT_TRIALS)
     if expect_codec is not None and (arith, rev) != tuple(int(v) for v in expect_codec):
         raise CodecMismatch(f"stream was coded with convolution arithmetic {ARITH_NAMES.get(arith, arith)} rev {rev}, this "
                             f"receiver runs {ARITH_NAMES.get(int(expect_codec[0]), expect_codec[0])} rev {int(expect_codec[1])}: "
@@ -203,7 +247,7 @@ def unpack_job(blob, expect_codec=None, expect_plan_revision=None):
     if sampler not in SAMPLER_NAMES:
         raise ValueError(f"corrupt job stream: unknown sampler id {sampler}")
     plan = crc = None
-    if fmt == FORMAT_JOB_INVARIANT:
+    if invariant:
         plan_id, plan_rev, crc = reader.unpack(_PLAN_HEAD)
         if plan_id not in PLANS:
             raise PlanMismatch(f"unknown generation plan id {plan_id} (this build reproduces {sorted(PLANS)} = "
@@ -212,19 +256,23 @@ def unpack_job(blob, expect_codec=None, expect_plan_revision=None):
             raise PlanMismatch(f"stream was generated under revision {plan_rev} of the {PLANS[plan_id]} plan, this receiver's "
                                f"kernels are revision {int(expect_plan_revision)}: its frames would not be the sender's")
         plan = (plan_id, plan_rev)
-    reader.need(2 * n_seg)
-    segments = []
+    n_trials = reader.unpack("<B")[0] if with_trials else 1
+    reader.need((3 if with_trials else 2) * n_seg)
+    segments, trials = [], []
     for _ in range(n_seg):
-        kind, n = reader.unpack("<BB")
+        kind, n, trial = reader.unpack("<BBB") if with_trials else reader.unpack("<BB") + (0,)
         if kind >= len(SEGMENT_KINDS):
             raise ValueError(f"corrupt job stream: unknown segment kind {kind}")
         segments.append((SEGMENT_KINDS[kind], n))
+        trials.append(trial)
     d = check_segments(segments, frames, n_key)
+    if with_trials:
+        check_trials(segments, trials, n_trials)
     key_strings = [KS.read(reader) for _ in range(n_key)]
     reader.end()
     return dict(format=fmt, plan=plan, crc=crc, codec=(arith, rev), noise_spec=spec, seed=seed, stream_id=stream_id, vid=vid, q=q, thr=thr,
                 sampler=SAMPLER_NAMES[sampler], subsample=subsample, denoise=bool(denoise), frames=frames, shape=(sh, sw),
-                segments=segments, d=d, key_strings=key_strings)
+                segments=segments, d=d, key_strings=key_strings, trials=trials, n_trials=n_trials)
 
 
 def job_file_name(vid, q, thr):

@@ -223,7 +223,9 @@ class ClipDecoder:
         All jobs advance in lockstep, as ``policy.run_policy`` advances them on the sender: each round every unfinished job
         executes its next segment.  The jobs whose segment is ("gen", n) are stacked along the batch axis of one
         ``generate`` call (``max_batch`` per launch), each drawing the noise of its own key (seed, stream id, start frame =
-        frames it holds so far, step) -- noise specification N1 -- and keep the first n frames; the jobs whose segment is
+        frames it holds so far, step) -- noise specification N1; a segment of noise trial t of a format-5 / format-6 stream
+        draws start frame + 65536 t, the one draw the sender chose: its K trials never multiply the receiver's work -- and
+        keep the first n frames; the jobs whose segment is
         ("key", n) decode its n frames in one ``decompress`` call per q (several jobs share a call up to ``max_batch``
         frames; a segment is never split).  ``models``: q -> ElicModel (default: this decoder's own model for every q);
         ``size`` = (H, W) of a frame (default: the generator's image size): the ELIC output is cropped to it, as the sender
@@ -235,7 +237,7 @@ class ClipDecoder:
         ``share=True`` does every distinct piece of work of a round once (the receiving side of ``run_policy(share=True)``;
         nothing in a stream says it was shared, and nothing is guessed).  A key frame is identified by (q, its string bytes):
         each distinct key frame of a round is decoded once, ``max_batch`` frames per call, whichever jobs name it.  A generation
-        state is (seed, stream id, format-4 flag, frames held, identities of the last two frames): the jobs of a state draw the
+        state is (seed, stream id, format-4 flag, frames held, noise trial, identities of the last two frames): the jobs of a state draw the
         same noise for the same conditioning frames, so one sample is generated per state (``max_batch`` states per launch)
         and each job keeps the first n frames its own segment names.  Streams of a sender with one noise stream per job have
         distinct stream ids and merge on key frames only.  Jobs advance by segment, so two jobs share a state only while they
@@ -267,6 +269,11 @@ class _RxJob:
     @property
     def segment(self):
         return self.stream["segments"][self.pos]
+
+    @property
+    def trial(self):
+        """The noise trial of the gen segment in execution (formats 5 / 6; 0 in a stream without trials)."""
+        return self.stream["trials"][self.pos] if self.stream.get("n_trials", 1) > 1 else 0
 
     def segment_strings(self):
         """Per frame of the key segment in execution, its strings."""
@@ -305,6 +312,8 @@ class _JobRounds:
                 raise ValueError(f"job stream v{job['vid']} q{job['q']} thr {job['thr']:.2f} was generated with "
                                  f"{job['sampler']}-{job['subsample']} denoise={job['denoise']}: build the decoder with them")
             Cn.check_segments(job["segments"], job["frames"], len(job["key_strings"]))
+            if job.get("n_trials", 1) > 1:
+                Cn.check_trials(job["segments"], job["trials"], job["n_trials"])
 
     def generation_round(self, gen):
         """gen: the jobs whose segment is ("gen", n).  One seed per noise launch, one generation plan per score-network launch;
@@ -312,14 +321,14 @@ class _JobRounds:
         launch_of = lambda j: (j.stream["seed"], j.stream.get("plan") is not None)      # noqa: E731
         for seed, inv in sorted({launch_of(j) for j in gen}):
             same = [j for j in gen if launch_of(j) == (seed, inv)]
-            states = self.grouper.group(same, self.share, state=lambda j: (j.stream["stream_id"], len(j.x), j.ids[-1], j.ids[-2]))
+            states = self.grouper.group(same, self.share, state=lambda j: (j.stream["stream_id"], len(j.x), j.trial, j.ids[-1], j.ids[-2]))
             self.count("job_rounds", len(same))
             self.count("samples", len(states))
             for c0 in range(0, len(states), self.max_batch):
                 part = states[c0:c0 + self.max_batch]
                 heads = [members[0] for _, members in part]                              # a state's members hold the same frames
                 cond = torch.stack([torch.stack(j.x[-2:], 0) for j in heads], 0).contiguous()
-                noise = P.n1_noise([(j.stream["stream_id"], len(j.x)) for j in heads], seed, self.decoder.device)
+                noise = P.n1_noise([(j.stream["stream_id"], P.trial_start(len(j.x), j.trial)) for j in heads], seed, self.decoder.device)
                 pred = self.decoder.generate(cond, groups=1, invariant=inv, noise_fn=noise)
                 assert pred.shape[1] * pred.shape[2] == self.channels
                 P.count_launch(self.stats, len(part))
@@ -327,7 +336,7 @@ class _JobRounds:
                     for j in members:                                                    # each keeps what its own segment names
                         n = j.segment[1]
                         j.x += [pred[k, t] for t in range(n)]
-                        j.ids += [P.gen_id(serial, t) for t in range(n)]
+                        j.ids += [P.gen_id(serial, t, j.trial) for t in range(n)]
 
     def decode_keys(self, q, strings, jobs):
         """strings: per frame, in launch order, of key frames of ``jobs`` -> the frames of one ``decompress`` call of q's model,

@@ -203,6 +203,7 @@ HIP_SYMBOLS = {
     "evc_ssim_workspace_bytes": (c_longlong, [c_int, c_int, c_int]),
     "evc_ssim_planes_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_double, c_void_p, c_void_p,
                                     c_void_p]),
+    "evc_frame_sqerr_f64": (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_void_p]),
     "evc_inception_stem_im2col_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     "evc_im2col_nhwc_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 11 + [c_void_p]),
     "evc_pool3x3s1p1_nhwc_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
@@ -1530,6 +1531,19 @@ def ssim_planes(a, b, taps, c1, c2, out=None):
     ws = torch.empty((max(1, nbytes // 8),), device=a.device, dtype=torch.float64)
     _check(L.evc_ssim_planes_f32(fptr(a), fptr(b), N, H, W, fptr(taps, torch.float64), float(c1), float(c2),
                                  fptr(out, torch.float64), ptr(ws), stream_ptr()), "evc_ssim_planes_f32")
+    return out
+
+
+def frame_sqerr(a, b, out=None):
+    """a, b: (n, ...) float32 frames on the device, contiguous -> out (n,) float64 on the device: per frame the sum of
+    ((double)a - (double)b)^2 (include/evc_hip.h evc_frame_sqerr_f64); a frame's value does not depend on the launch."""
+    n = int(a.shape[0])
+    assert a.dim() >= 1 and a.shape == b.shape and n > 0 and a.numel() > 0
+    if out is None:
+        out = torch.empty((n,), device=a.device, dtype=torch.float64)
+    assert out.shape == (n,)
+    _check(hip_lib().evc_frame_sqerr_f64(fptr(a), fptr(b), n, a.numel() // n, fptr(out, torch.float64), stream_ptr()),
+           "evc_frame_sqerr_f64")
     return out
 
 

@@ -19,6 +19,12 @@ Shared rounds (``noise_streams="group", share=True``): all thresholds of one (vi
 that hold the same frames would generate the same chunk; ``StateGrouper`` finds them by the identity of their last two frames
 and each round generates once per distinct state instead of once per job.
 
+Noise trials (``trials=K``, noise="evc"): the sender knows the original, so it draws every round K times -- trial t keys N1 with
+start frame + 65536 t, trial 0 is the plain key -- in the same launches, and each job keeps the draw ``choose_trial`` prefers
+under its own threshold: the longest accepted prefix, then the better mean, then the lowest trial.  The job's program names the
+trial of every generated segment (container formats 5 / 6) for ceil(log2 K) bits, which ``bpp`` includes; a receiver generates
+the chosen draw only.  ``PsnrDeviceMetric`` judges the K-fold candidates where they are (csrc/metric.hip).
+
 Metrics: ``PsnrMetric`` is the reference's ``decide_5to5`` rule (accept while PSNR >= threshold, cal_psnr of
 city_sender.py:257-260).  ``CallableMetric`` is the hook for ``decide_5to5_lpips`` (accept while distance <=
 threshold): LPIPS needs torchvision's pretrained AlexNet, which cannot be fetched offline, so the metric is supplied
@@ -48,6 +54,23 @@ class PsnrMetric:
     def accept(value, thr):
         return value >= thr
 
+    @staticmethod
+    def better(a, b):
+        """Whether value a is strictly better than b: the higher PSNR."""
+        return a > b
+
+
+class PsnrDeviceMetric(PsnrMetric):
+    """PsnrMetric with the sum on the device: ``lib.frame_sqerr`` (csrc/metric.hip) adds every frame's squared error in
+    float64 and n doubles come back instead of the frames; 10 log10(1 / mse) is formed on the host in float64.  The sweep with
+    noise trials judges K times the candidates and uses this class; ``PsnrMetric`` stays the default."""
+
+    def values(self, pred, gt):
+        pred, gt = pred.detach().float().contiguous(), gt.detach().float().contiguous()
+        sums = L.frame_sqerr(pred, gt).cpu().numpy()
+        with np.errstate(divide="ignore"):          # identical frames: 10 log10(1 / 0) = inf, as cal_psnr
+            return 10 * np.log10(1.0 / (sums / (pred.numel() // pred.shape[0])))
+
 
 class CallableMetric:
     """decide_5to5_lpips (city_sender.py:376-406): kept while distance(pred, gt) <= threshold.  ``fn(pred, gt)`` takes
@@ -64,6 +87,11 @@ class CallableMetric:
     @staticmethod
     def accept(value, thr):
         return value <= thr
+
+    @staticmethod
+    def better(a, b):
+        """Whether value a is strictly better than b: the smaller distance."""
+        return a < b
 
 
 def load_metric(policy, spec=None, device="cuda", net="alex"):
@@ -105,7 +133,7 @@ def load_metric(policy, spec=None, device="cuda", net="alex"):
 
 
 class _Job:
-    __slots__ = ("uid", "sid", "vid", "q", "thr", "x", "ids", "d", "bits", "round", "segments", "strings")
+    __slots__ = ("uid", "sid", "vid", "q", "thr", "x", "ids", "d", "bits", "round", "segments", "strings", "trials")
 
     def __init__(self, uid, vid, q, thr, sid=None):
         self.uid, self.vid, self.q, self.thr = uid, vid, q, thr
@@ -113,6 +141,7 @@ class _Job:
         self.x, self.d, self.bits, self.round = [], [], [], 0
         self.ids = []                                   # identity of every frame of ``x`` (StateGrouper)
         self.segments, self.strings = [], []
+        self.trials = []                                # per segment: the noise trial a gen segment was drawn with, 0 for key
 
 
 def key_id(vid, q, f):
@@ -120,9 +149,9 @@ def key_id(vid, q, f):
     return ("key", vid, q, f)
 
 
-def gen_id(serial, t):
-    """Identity of frame t of the chunk generated for the state with that serial number."""
-    return ("gen", serial, t)
+def gen_id(serial, t, trial=0):
+    """Identity of frame t of the chunk generated, under noise trial ``trial``, for the state with that serial number."""
+    return ("gen", serial, t, trial)
 
 
 class StateGrouper:
@@ -158,8 +187,48 @@ class StateGrouper:
         return states
 
 
+TRIAL_SHIFT = 16                   # noise trial t of a round: start frame + 65536 t in the N1 key (trial 0 = the plain key)
+MAX_TRIALS = 255                   # a job stream names the trial in one byte
+
+
+def trial_start(held, trial):
+    """The start-frame word of the N1 key of noise trial ``trial`` of the round a job starts holding ``held`` frames."""
+    return int(held) | int(trial) << TRIAL_SHIFT
+
+
+def trial_bits(segments, n_trials):
+    """Side information of the noise trials of one job: ceil(log2 K) bits per generated segment."""
+    return sum(1 for kind, _ in segments if kind == "gen") * (int(n_trials) - 1).bit_length()
+
+
+def choose_trial(values, thr, metric):
+    """values[t][f]: the metric of candidate frame f under noise trial t; -> (trial, accepted).  a_t = the length of trial t's
+    accepted prefix under ``thr``.  The largest a_t wins; among equals the better mean metric over those a_t frames
+    (``metric.better``); among equals the lowest trial.  (None, 0) when no trial's first frame is accepted."""
+    best, best_a, best_mean = None, 0, None
+    for t, a in enumerate(accepted_prefixes(values, thr, metric)):
+        if a == 0 or a < best_a:
+            continue
+        mean = float(np.mean(np.asarray(values[t][:a], dtype=np.float64)))
+        if a > best_a or metric.better(mean, best_mean):
+            best, best_a, best_mean = t, a, mean
+    return best, best_a
+
+
+def accepted_prefixes(values, thr, metric):
+    """a_t of ``choose_trial`` for every trial: the frames accepted before the first one that is not."""
+    out = []
+    for row in values:
+        a = 0
+        while a < len(row) and metric.accept(row[a], thr):
+            a += 1
+        out.append(a)
+    return out
+
+
 def n1_noise(pairs, seed, device):
-    """Noise specification N1 for one launch: pairs = per sample (stream id, start frame = frames held when the round starts)
+    """Noise specification N1 for one launch: pairs = per sample (stream id, start frame = frames held when the round starts;
+    ``trial_start`` for a noise trial)
     -> ``noise_fn(tag, shape)`` of ``ClipDecoder.generate``.  The keys go up once; every step is one launch for the whole batch
     (step 0 = x_T, step i + 1 = the noise of sampler step i).  Sender and receiver both draw through here."""
     keys = L.noise_keys(pairs, device)
@@ -175,7 +244,7 @@ def count_launch(stats, samples):
 
 def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=30, max_batch=32, seed=0,
                bpp_limit=1.0, device="cuda", log=None, noise_source=None, stats=None, noise="torch", batch_invariant=False,
-               noise_streams="job", share=False, estimate=False):
+               noise_streams="job", share=False, estimate=False, trials=1):
     """The reference's sweep, batched.
 
     decoder:       ClipDecoder (only ``generate`` is used: the generator does not depend on q)
@@ -211,11 +280,21 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
     estimate:      key frames go through ``estimated_batch`` instead of ``coded_batch`` (--entropy-estimation): the same frames,
                    ``bits`` are float estimates and there are no strings (``key_strings`` holds None: such results cannot be
                    packed into job streams)
+    trials:        K noise trials per round (needs noise="evc" without ``noise_source``, K <= max_batch, K <= 255).  Every state of
+                   a round is generated K times in the same launches -- the conditioning pair repeated, trial t drawing the key
+                   (seed, stream id, start frame + 65536 t, step), trial 0 today's key; ``max_batch`` counts samples, so a launch
+                   holds max_batch // K states --, the metric is evaluated once per (state, trial, frame), and every member job
+                   keeps the frames of the trial ``choose_trial`` picks under its own threshold.  The trial is part of a frame's
+                   identity (``gen_id``), so under ``share`` two jobs are one state only if they kept the same trial's frames.
+                   Results carry ``n_trials`` = K, ``trials`` (per segment: 0 for key, the chosen trial for gen) and
+                   ``trial_bits`` = gen segments x ceil(log2 K), which ``bpp`` and the ``bpp_limit`` cut include;
+                   ``stats["trial_prefixes"]`` lists per executed job-round (a_0 .. a_{K-1}, chosen).  K = 1 is the sweep as it
+                   always was, bit for bit
     stats:         optional dict, filled with the launch-size histogram {samples (= states) in a launch: generation launches},
                    the number of generation rounds and of key frames coded, the host seconds spent drawing noise, and per
                    round the number of states generated (``states``) and of active jobs they served (``jobs_served``)
     Returns {(vid, q): [dict(thr, x (frames,3,H,W) float32 numpy, d (frames,) int, bits [..], bpp, segments, stream_id,
-    seed, key_strings, shape)]} with, per (vid, q), the thresholds in the given order cut at the first one whose rate reaches
+    seed, key_strings, shape, n_trials, trials, trial_bits)]} with, per (vid, q), the thresholds in the given order cut at the first one whose rate reaches
     ``bpp_limit`` bits per pixel (``if NN_bpp >= 1.0: break``, city_sender.py:563-564).  ``segments`` is the job's program in
     order: ("key", n) for n key frames decoded in one ELIC call (the initial pair, each fall-back pair, 1 at the clip's
     end), ("gen", n) for a round of which n >= 1 frames were kept (a rejected round leaves no frame and no entry: its noise
@@ -232,6 +311,18 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
     if share and noise_streams != "group":
         raise ValueError("share=True needs noise_streams='group': jobs that draw from streams of their own never generate "
                          "the same frames, so there is nothing to share")
+    trials = int(trials)
+    if trials < 1:
+        raise ValueError(f"trials must be >= 1, not {trials}")
+    if trials > 1:
+        if noise != "evc" or noise_source is not None:
+            raise ValueError("trials > 1 needs noise='evc' and no noise_source: the receiver regenerates the chosen draw from the "
+                             "trial number alone, which only the keyed noise of specification N1 allows")
+        if trials > max_batch:
+            raise ValueError(f"trials = {trials} > max_batch = {max_batch}: the trials of a state ride in one launch, and "
+                             "max_batch counts samples")
+        if trials > MAX_TRIALS:
+            raise ValueError(f"trials = {trials} > {MAX_TRIALS}: a job stream names the trial in one byte")
     if batch_invariant:
         decoder._refuse_recovery()
     if noise == "evc" and noise_source is None:
@@ -271,6 +362,7 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
             job.ids.append(key_id(job.vid, job.q, f))
         if len(fs):
             job.segments.append(("key", len(fs)))
+            job.trials.append(0)
 
     ensure_keys({(j.vid, j.q, f) for j in jobs for f in (0, 1)})          # city_sender.py:521-524
     for j in jobs:
@@ -278,17 +370,17 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
 
     def _noise_for(batch):
         if noise == "evc" and noise_source is None:
-            return n1_noise([(j.sid, len(j.x)) for j in batch], seed, device)
+            return n1_noise([(j.sid, trial_start(len(j.x), t)) for j, t in batch], seed, device)
 
         def fn(tag, shape):      # one counter-based stream per (job, round, step) -- per (group, start frame, step) under group
             # streams --: independent of the batch composition
             step = 0 if tag == "init" else int(tag) + 1
             out = torch.empty(shape, device=device, dtype=torch.float32)
             if noise_source is not None:
-                for i, j in enumerate(batch):
+                for i, (j, _) in enumerate(batch):
                     out[i] = noise_source((j.vid, j.q, j.thr), j.round, step, tuple(shape[1:])).to(device)
                 return out
-            for i, j in enumerate(batch):
+            for i, (j, _) in enumerate(batch):
                 g = torch.Generator(device=device)
                 at = len(j.x) if noise_streams == "group" else j.round
                 g.manual_seed(((((int(seed) & 0xFFFFF) << 20 | j.sid) << 6 | at) << 10 | step) & (2 ** 63 - 1))
@@ -315,31 +407,36 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
             break
         states = grouper.group(active, share)            # [(serial, members)]: one generated sample per state
         fallback = []
-        for c0 in range(0, len(states), max_batch):
-            part = states[c0:c0 + max_batch]
-            batch = [members[0] for _, members in part]                                       # a state's members hold the same frames
-            cond = torch.stack([torch.stack(j.x[-2:], 0) for j in batch], 0).contiguous()     # (n, 2, 3, H, W)
+        per_launch = max_batch // trials                 # max_batch counts samples: a state's K trials share its launch
+        for c0 in range(0, len(states), per_launch):
+            part = states[c0:c0 + per_launch]
+            heads = [members[0] for _, members in part]                                       # a state's members hold the same frames
+            batch = [(j, t) for j in heads for t in range(trials)]                            # sample k * K + t: state k, noise trial t
+            cond = torch.stack([torch.stack(j.x[-2:], 0) for j, _ in batch], 0).contiguous()  # (n, 2, 3, H, W)
             pred = decoder.generate(cond, noise_fn=noise_for(batch), groups=1,              # (n, 5, 3, H, W)
                                     invariant=True if batch_invariant else None)
             count_launch(stats, len(batch))
-            n_new = [min(pred.shape[1], frames - len(j.x)) for j in batch]
+            n_new = [min(pred.shape[1], frames - len(j.x)) for j, _ in batch]
             flat_p = torch.cat([pred[k, :n_new[k]] for k in range(len(batch))], 0)
-            flat_g = torch.cat([gt_dev[j.vid][len(j.x):len(j.x) + n_new[k]] for k, j in enumerate(batch)], 0)
+            flat_g = torch.cat([gt_dev[j.vid][len(j.x):len(j.x) + n_new[k]] for k, (j, _) in enumerate(batch)], 0)
             vals = metric.values(flat_p, flat_g)                 # every candidate frame of the launch in one call
             o = 0
             for k, (serial, members) in enumerate(part):
+                n = n_new[k * trials]
+                table = [vals[o + t * n:o + (t + 1) * n] for t in range(trials)]          # [trial][frame]
                 for j in members:                                # each member judges the state's candidates by its own threshold
-                    acc = 0
-                    for t in range(n_new[k]):
-                        if not metric.accept(vals[o + t], j.thr):
-                            break
-                        j.x.append(pred[k, t]); j.ids.append(gen_id(serial, t)); j.d.append(0); acc += 1
+                    trial, acc = choose_trial(table, j.thr, metric)
+                    for t in range(acc):
+                        j.x.append(pred[k * trials + trial, t]); j.ids.append(gen_id(serial, t, trial)); j.d.append(0)
                     j.round += 1
                     if acc:
                         j.segments.append(("gen", acc))
+                        j.trials.append(trial)
                     if acc == 0:
                         fallback.append(j)
-                o += n_new[k]
+                    if trials > 1 and stats is not None:
+                        stats.setdefault("trial_prefixes", []).append((tuple(accepted_prefixes(table, j.thr, metric)), trial))
+                o += n * trials
         if fallback:                 # city_sender.py:538-548: key-code the next two frames
             ensure_keys({(j.vid, j.q, f) for j in fallback for f in (len(j.x), len(j.x) + 1) if f < frames})
             for j in fallback:
@@ -358,13 +455,15 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
         lst = out.setdefault((j.vid, j.q), [])
         if lst and lst[-1] is None:
             continue                                            # sweep of this (vid, q) already cut
-        bpp = sum(j.bits) / H / W / frames
+        side = trial_bits(j.segments, trials)
+        bpp = (sum(j.bits) + side) / H / W / frames
         if bpp >= bpp_limit:
             lst.append(None)
             continue
         lst.append(dict(thr=j.thr, x=torch.stack(j.x[:frames], 0).cpu().numpy(), d=np.asarray(j.d[:frames], dtype=np.int64),
                         bits=list(j.bits), bpp=bpp, segments=list(j.segments), stream_id=j.sid, seed=int(seed),
-                        key_strings=list(j.strings), shape=shapes[0], invariant=bool(batch_invariant)))
+                        key_strings=list(j.strings), shape=shapes[0], invariant=bool(batch_invariant),
+                        n_trials=trials, trials=list(j.trials), trial_bits=side))
     return {k: [r for r in v if r is not None] for k, v in out.items()}
 
 

@@ -1,5 +1,6 @@
 """Receiver for policy-coded clips: decodes the job streams a ``city_sender.py --policy psnr|lpips --bitstream-dir DIR`` run
-wrote (container format 3, or 4 for jobs generated with ``--batch-invariant``; one file per reported (video, q, threshold)
+wrote (container format 3, or 4 for jobs generated with ``--batch-invariant``; 5 and 6 are those of a ``--noise-trials K``
+sweep, whose generated segments name the one draw the receiver makes; one file per reported (video, q, threshold)
 job) with nothing but the model files.  A format-4 job is decoded on the score network's batch-invariant view, whatever
 ``--batch`` is; the CRC-32 of its frames is compared with the sender's and ``frames: match`` / ``frames: MISMATCH`` printed
 per job (any mismatch makes the exit status non-zero).
@@ -35,6 +36,8 @@ def write_job_streams(directory, results, models, sampler, cfg):
             if r.get("invariant"):       # format 4: the plan the frames were generated under, and their checksum
                 from . import lib as L
                 extra = dict(plan=(container.PLAN_INVARIANT, L.invariant_plan_revision()), crc=container.frames_crc(r["x"]))
+            if r.get("n_trials", 1) > 1:     # formats 5 / 6: the noise trial every generated segment was drawn with
+                extra.update(trials=r["trials"], n_trials=r["n_trials"])
             blob = container.pack_job(r["segments"], r["key_strings"], r["shape"], models[q].codec_tag(), r["seed"],
                                       r["stream_id"], vid, q, r["thr"], sampler, getattr(cfg.sampling, "subsample", None) or 0,
                                       cfg.sampling.denoise, **extra)

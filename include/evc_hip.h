@@ -658,6 +658,19 @@ long long evc_ssim_workspace_bytes(int N, int H, int W);
 int evc_ssim_planes_f32(const float* a, const float* b, int N, int H, int W, const double* taps11, double c1, double c2,
                         double* out, void* ws, void* stream);
 
+/* ---- Per-frame squared error: the sum under the sender's PSNR rule (csrc/metric.hip) ---------
+ * a, b: n contiguous rows (frames) of `elems` fp32 each; out[i] = sum over frame i of ((double)a - (double)b)^2, i.e.
+ * elems times the float64 mse of cal_psnr.  One workgroup per frame; the elements are cut into chunks of four by their
+ * index in the frame, thread t of 1024 takes chunks t, t + 1024, ... with one partial per position in the chunk, the
+ * partials are added in a fixed order (per thread, wave shuffle tree, the 16 wave totals in turn) and stored plainly: no
+ * atomics and no workspace.  The order depends on elems only, so out[i] is the same bit pattern whatever n is, whichever
+ * row the frame is and wherever the row starts; any elems >= 1 is taken, a chunk is fetched with one 16-byte load where its
+ * address allows and with 4-byte loads elsewhere (rows of odd elems, unaligned bases).  The sum differs from the exact one
+ * by at most (elems + 1) * 2^-53 relative.  Nothing is clamped or dropped: a NaN or inf - inf in a frame makes that frame's
+ * sum NaN, inf against a finite value makes it inf, other frames are unaffected.  Caller's stream, no allocation;
+ * EVC_EINVAL before the launch for a null pointer, n <= 0 or elems <= 0.  n * elems may exceed 2^31. */
+int evc_frame_sqerr_f64(const float* a, const float* b, int n, long long elems, double* out, void* stream);
+
 /* ---- FID and precision / recall: the Inception-v3 feature network (csrc/inception.hip) ------
  * The reference's evaluation/ package: pytorch-fid's InceptionV3 (inception.py:84-163 the four blocks, :184-328 the patched
  * Inception blocks), the features of fid_PR.py:110-167 and the k-NN precision / recall of pr.py.  Activations are NHWC, the
