@@ -24,6 +24,10 @@ for bit, on the GPU (csrc/resample.hip); ``--data_frames '
 ``--yuv-fit tile`` codes the whole frame instead: it is cut into overlapping tiles of the model's size on the GPU (csrc/tile.hip),
 every tile's frames are a video of their own (video index = clip * tiles + tile), ``tiles.json`` records the grid and
 ``city_stitch.py`` (stitch.py) blends the receiver's decoded tiles back into full frames.
+``--yuv-fit joint`` codes the whole frame as one video of its own size: the score network is wrapped in ``tiled.TiledScoreNet``,
+whose eps at a pixel is the tent-weighted mean over the overlapping tiles that cover it, so the tiles are generated jointly, key
+frames are coded once at the frame's size, ``canvas.json`` records size and grid for ``city_receiver.py --yuv-fit joint`` and
+nothing is stitched (DESIGN.md section 8c "Joint generation").
 ``--entropy-estimation`` (a reference flag) reports every key frame's rate as the sum of -log2(likelihood), computed on the GPU
 (``ElicModel.estimate``) instead of the length of range-coded strings: same frames, fractional bits.
 ``--ssim`` adds the reference's SSIM (fvd_utils/calculate_ssim.py; ssim.py, csrc/ssim.hip) of every job:
@@ -179,17 +183,21 @@ def add_yuv_input_flags(p):
                    help="raw .yuv only: WxH[@fps][:bits], e.g. 128x128@30:8 (default: from a _<W>x<H>_<fps>Hz_<bits>bit_ file name)")
     p.add_argument("--yuv-upsample", choices=["bicubic", "bilinear", "nearest"], default="bicubic",
                    help="chroma up-sampling of --data_yuv (torch semantics, align_corners=False; the reference uses bicubic)")
-    p.add_argument("--yuv-fit", choices=["refuse", "crop", "tile"], default="refuse",
+    p.add_argument("--yuv-fit", choices=["refuse", "crop", "tile", "joint"], default="refuse",
                    help="--data_yuv / --data_frames of another frame size than config.data.image_size: refuse (default) ends the "
                         "run; crop fits every frame as the reference's read_video does (bench_uvg.py:577-598) -- the 8-bit RGB "
                         "frame is centre-cropped to a square and resized as PIL.Image.resize does, bit for bit, on the GPU "
                         "(csrc/resample.hip); tile codes the whole frame: it is cut into overlapping image_size x image_size "
                         "tiles on the GPU (csrc/tile.hip) and every tile's 30 frames are a video of their own, video index = "
                         "clip * tiles + tile (--start_idx / --end_idx count these); the sender writes tiles.json, and "
-                        "city_stitch.py blends the receiver's decoded tiles back into full frames.  A file that already has "
-                        "the size is read as without the flag")
+                        "city_stitch.py blends the receiver's decoded tiles back into full frames; joint codes the whole "
+                        "frame as ONE video of its own size (video index = clip): the score network's eps at a pixel is the "
+                        "tent-weighted mean over the overlapping tiles that cover it (tiled.py), so the tiles are generated "
+                        "jointly, key frames are coded once at the frame's size and nothing is stitched; the sender writes "
+                        "canvas.json, which city_receiver.py --yuv-fit joint reads.  A file that already has the size is read "
+                        "as without the flag")
     p.add_argument("--yuv-tile-overlap", type=int, default=16, metavar="O",
-                   help="--yuv-fit tile: samples by which neighbouring tiles overlap at least (even, 0 .. image_size / 2; "
+                   help="--yuv-fit tile / joint: samples by which neighbouring tiles overlap at least (even, 0 .. image_size / 2; "
                         "default 16)")
     p.add_argument("--yuv-resize", choices=["lanczos", "bicubic", "bilinear", "hamming", "box"], default="lanczos",
                    help="--yuv-fit crop: Pillow's resampling filter (the reference uses lanczos)")
@@ -203,8 +211,9 @@ def _given(argv, flag):
     return any(a == flag or a.startswith(flag + "=") for a in argv)
 
 
-def parse_args(argv=None, parser=None):
-    """``build_parser().parse_args`` plus what argparse cannot say: --data_yuv replaces --data_npy, it does not join it."""
+def parse_args(argv=None, parser=None, receiver=False):
+    """``build_parser().parse_args`` plus what argparse cannot say: --data_yuv replaces --data_npy, it does not join it.
+    receiver: the arguments are city_receiver.py's, where ``--yuv-fit joint`` needs no source (canvas.json names the size)."""
     p = parser or build_parser()
     argv = sys.argv[1:] if argv is None else list(argv)
     args = p.parse_args(argv)
@@ -214,13 +223,18 @@ def parse_args(argv=None, parser=None):
         p.error("--data_frames replaces --data_npy and --data_yuv: pass one of the three")
     if args.yuv_geometry and not args.data_yuv:
         p.error("--yuv-geometry describes the --data_yuv file: pass --data_yuv")
-    if args.yuv_fit in ("crop", "tile") and not (args.data_yuv or args.data_frames):
+    if (args.yuv_fit in ("crop", "tile") or args.yuv_fit == "joint" and not receiver) and not (args.data_yuv or args.data_frames):
         p.error("--yuv-fit fits the frames of --data_yuv or --data_frames: pass one of them")
     if _given(argv, "--yuv-resize") and args.yuv_fit != "crop":
         p.error("--yuv-resize names the filter of --yuv-fit crop: pass --yuv-fit crop")
-    if _given(argv, "--yuv-tile-overlap") and args.yuv_fit != "tile":
-        p.error("--yuv-tile-overlap is the overlap of --yuv-fit tile: pass --yuv-fit tile")
-    if args.yuv_fit == "tile":
+    if _given(argv, "--yuv-tile-overlap") and args.yuv_fit not in ("tile", "joint"):
+        p.error("--yuv-tile-overlap is the overlap of --yuv-fit tile / joint: pass --yuv-fit tile or --yuv-fit joint")
+    if args.yuv_fit == "joint":
+        from .recovery import recovery_mode
+        if recovery_mode(getattr(args, "range_recovery", None)) == "layer":
+            p.error("--yuv-fit joint does not combine with --range-recovery layer: recovery is not built for a network that runs "
+                    "a frame as several launches per step; set EVC_CONV_ARITH=bf16x6 (no range assumption) instead")
+    if args.yuv_fit in ("tile", "joint"):
         size = _config_image_size(args)
         if args.yuv_tile_overlap < 0 or args.yuv_tile_overlap % 2 or (size is not None and 2 * args.yuv_tile_overlap > size):
             p.error(f"--yuv-tile-overlap {args.yuv_tile_overlap} must be even and inside [0, image_size / 2]"
@@ -240,7 +254,8 @@ def _config_image_size(args):
 
 def load_yuv_clips(args, image_size, log=print):
     """The clips of ``--data_yuv`` (or ``--data_frames``) as the (B, 30, 3, H, W) uint8 array --data_npy would have held, and the
-    file's frame rate (30 for image frames).  Under ``--yuv-fit tile`` the videos are the tiles' (video_io.read_clips)."""
+    file's frame rate (30 for image frames).  Under ``--yuv-fit tile`` the videos are the tiles' (video_io.read_clips); under
+    ``--yuv-fit joint`` the frames keep their own size (H, W), whatever the model's."""
     from . import video_io as V
     fit = dict(fit="crop", size=image_size, resize=args.yuv_resize) if args.yuv_fit == "crop" else {}
     if args.yuv_fit == "tile":
@@ -249,18 +264,24 @@ def load_yuv_clips(args, image_size, log=print):
         except ValueError as e:
             sys.exit(f"--yuv-tile-overlap: {e}")
         fit = dict(fit="tile", size=image_size, overlap=args.yuv_tile_overlap)
+    joint = args.yuv_fit == "joint"          # the frames are read at their own size: one video per clip (tiled.py)
+    if joint:
+        try:
+            V.check_overlap(image_size, args.yuv_tile_overlap)
+        except ValueError as e:
+            sys.exit(f"--yuv-tile-overlap: {e}")
     if args.data_frames:
         try:
             data = V.read_frame_clips(args.data_frames, log=log, **fit)
         except V.VideoFormatError as e:
             sys.exit(f"--data_frames: {e}")
-        if data.shape[-2:] != (image_size, image_size):
+        if data.shape[-2:] != (image_size, image_size) and not joint:
             sys.exit(f"--data_frames {args.data_frames}: frames are {data.shape[-1]}x{data.shape[-2]}, the model's "
                      f"config.data.image_size is {image_size}: pass --yuv-fit crop to centre-crop and resize them")
         return data, 30
     try:
         v = V.open_video(args.data_yuv, args.yuv_geometry)
-        if (v.height, v.width) != (image_size, image_size) and not fit:
+        if (v.height, v.width) != (image_size, image_size) and not fit and not joint:
             sys.exit(f"--data_yuv {args.data_yuv}: frames are {v.width}x{v.height}, the model's config.data.image_size is "
                      f"{image_size}; resizing is not built (the reference resizes with ffmpeg / PIL, which cannot be reproduced "
                      f"here): scale the file to {image_size}x{image_size} first, or pass --yuv-fit crop to centre-crop and "
@@ -290,6 +311,22 @@ def write_tile_manifests(args, image_size, videos, fps, log=print):
     m["clips"] = videos // (m["ny"] * m["nx"])
     for d in filter(None, (args.output_path, args.bitstream_dir)):
         log(f"tile manifest: {V.write_manifest(d, m)}")
+    return m
+
+
+def joint_canvas(args, image_size, data, fps, rank=0, log=print):
+    """``--yuv-fit joint`` on frames of another size than the model's: the grid line, canvas.json into --output_path and
+    --bitstream-dir (rank 0) and the manifest; None when the flag is absent or the source already has the model's size (the run
+    is then what it is without the flag, and nothing is written)."""
+    from . import video_io as V
+    if args.yuv_fit != "joint" or tuple(data.shape[-2:]) == (image_size, image_size):
+        return None
+    height, width = data.shape[-2:]
+    m = V.tile_manifest(width, height, image_size, args.yuv_tile_overlap, len(data), 30, fps, args.data_yuv or args.data_frames)
+    log(V.canvas_line(width, height, image_size, args.yuv_tile_overlap, m["oy"], m["ox"]))
+    if rank == 0:
+        for d in filter(None, (args.output_path, args.bitstream_dir)):
+            log(f"canvas manifest: {V.write_manifest(d, m, V.CANVAS_NAME)}")
     return m
 
 
@@ -492,7 +529,8 @@ def report_jobs(run, jobs, more=None, trials=None):
     a --noise-trials sweep, (K, trial bits): the bits join the job's BPP and its first line says so."""
     values = run.measurer.measure_jobs([(vid, x, gt) for vid, _, _, x, gt, _, _ in jobs])
     for i, ((vid, q, thr, x, gt, bits, d), v, extra) in enumerate(zip(jobs, values, more or [{}] * len(jobs))):
-        bpp = (sum(bits) if trials is None else sum(bits) + trials[i][1]) / 128 / 128 / 30
+        pixels = getattr(run, "pixels", None) or 128 * 128         # --yuv-fit joint: the frame's own H x W
+        bpp = (sum(bits) if trials is None else sum(bits) + trials[i][1]) / pixels / 30
         lines = R.sender_lines(v, d, bpp, run.measurer.net)
         if trials is not None:
             lines[0] += f" trials {trials[i][0]} (+{trials[i][1]} bits)"
@@ -540,7 +578,8 @@ def run_mask_policy(run, net, models, cfg, data, vids, device, gen):
                     fh.write(container.pack(mask, keys, shape, codec=model.codec_tag()))
                 with open(path, "rb") as fh:          # refuses a stream coded under another arithmetic
                     d_rx, keys_rx, shape_rx = container.unpack(fh.read(), expect_codec=model.codec_tag())
-            frames = dec.decode(d_rx, keys_rx, shape_rx, generator=gen, key_frames=key_frames)[..., :gt.shape[-2], :gt.shape[-1]]
+            crop = dict(size=tuple(gt.shape[-2:])) if getattr(run, "pixels", None) else {}       # --yuv-fit joint: generate at H x W
+            frames = dec.decode(d_rx, keys_rx, shape_rx, generator=gen, key_frames=key_frames, **crop)[..., :gt.shape[-2], :gt.shape[-1]]
             check_numerics(frames, f"videos {chunk[0]}..{chunk[-1]} q{q}", recovery_note(dec))
             x_all = frames.cpu().numpy()
             per_key = est_bits if args.entropy_estimation else [[KS.bits(s) for s in KS.split(k)] for k in keys]
@@ -625,6 +664,13 @@ def main(argv=None):
     net, models = load_models(args, cfg, rank, world, device)
     log = lambda m: print(f"[rank {rank}] {m}", flush=True)  # noqa: E731
     data, yuv_fps = load_data(args, cfg, rank, log)
+    canvas = joint_canvas(args, cfg.data.image_size, data, yuv_fps, rank, log) if args.data_yuv or args.data_frames else None
+    if canvas is not None:       # the network takes whole frames: eps blended over the tiles that cover a pixel (tiled.py)
+        from .tiled import TiledScoreNet
+        try:
+            net = TiledScoreNet(net, cfg.data.image_size, args.yuv_tile_overlap, tile_batch=max(1, args.batch))
+        except NotImplementedError as e:
+            sys.exit(f"--yuv-fit joint: {e}")
     # ---- this rank's videos under one of the two policies ----
     lo, hi = D.shard_range(args.end_idx + 1 - args.start_idx, rank, world)
     vids = list(range(args.start_idx + lo, args.start_idx + hi))
@@ -632,6 +678,7 @@ def main(argv=None):
     t_start = time.time()
     run = SimpleNamespace(args=args, log=log, fps=yuv_fps, measurer=R.Measurer(ssim=args.ssim, fid_dims=args.fid_dims, yuv=args.yuv_metrics, **nets))
     run.collector = R.Collector(net=run.measurer.net)
+    run.pixels = canvas["width"] * canvas["height"] if canvas is not None else None       # of a frame, for BPP (None: 128 x 128)
     if args.policy == "mask":
         run_mask_policy(run, net, models, cfg, data, vids, device, gen)
     else:

@@ -5,6 +5,8 @@
 //                        dst[t][n][c][y][x] = src[n][c][min(oy[ty] + y, H - 1)][min(ox[tx] + x, W - 1)],  t = ty * nx + tx
 //   evc_tile_blend_f32   tiles (ny * nx, N, 3, S, S) fp32 -> out (N, 3, H, W) fp32, the tent-weighted mean of the tiles that
 //                        cover a pixel
+//   evc_tile_gather_f32  the gather for fp32 planes of any channel count: src (N, C, H, W) -> dst (ny * nx, N, C, S, S), the same
+//                        copy (joint generation, tiled.py: the noisy state and the conditioning frames of a whole canvas)
 //
 // The blend of one output pixel (y, x): with the integer tent t(i) = min(i + 1, S - i), the tiles that cover the pixel are
 // visited in ascending tile index; acc = acc + float(t(ly) * t(lx)) * v (the product rounded, then the sum: no contraction),
@@ -19,6 +21,10 @@
 // The blend reads a tile's 4 values as one 16-byte load where the group lies inside the tile at an aligned address, else the
 // covered ones one by one.  The origins are read from the device arrays and held inside [0, max(L - S, 0)] whatever they
 // say, so nothing outside src / tiles is read even if they differ from the host arrays that were checked.
+// The fp32 gather is ONE kernel for every shape: a thread owns 4 consecutive floats of the packed destination.  Where the four
+// lie in one tile row, their source columns lie inside the row and both addresses are 16-byte aligned they move as one
+// 16-byte load and store; elsewhere (odd W, an origin or an S that is no multiple of 4, the edge replication of a short axis,
+// a group that runs over the end of a tile row) each float is located on its own and moves alone under the clamp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/evc_hip.h"
@@ -80,6 +86,42 @@ tile_gather_kernel(const uint8_t* __restrict__ src, int N, int H, int W, int S, 
         }
     } else {
         *d = row[min(x0 + x, W - 1)];
+    }
+}
+
+// Where float ``idx`` of the packed destination (t, plane, y, x) comes from: its source row (clamped) and, in x0 / x, the tile's
+// column origin and the column inside the tile.  planes = N * C.
+__device__ __forceinline__ const uint32_t* gather_row(const uint32_t* __restrict__ src, long long idx, long long planes, int H, int W,
+                                                      int S, int nx, const int* __restrict__ oy, const int* __restrict__ ox, int& x0,
+                                                      int& x) {
+    x = (int)(idx % S);
+    long long r = idx / S;
+    const int y = (int)(r % S);
+    r /= S;
+    const long long plane = r % planes, t = r / planes;
+    const int y0 = origin(oy, (int)(t / nx), H, S);
+    x0 = origin(ox, (int)(t % nx), W, S);
+    return src + (plane * H + min(y0 + y, H - 1)) * W;
+}
+
+// One thread per 4 consecutive destination floats (the last group of an odd total is short).  The samples move as 32-bit words:
+// a copy, whatever their bits mean.
+__global__ void __launch_bounds__(THREADS)
+tile_gather_f32_kernel(const uint32_t* __restrict__ src, long long planes, int H, int W, int S, int nx, const int* __restrict__ oy,
+                       const int* __restrict__ ox, uint32_t* __restrict__ dst, long long total) {
+    const long long g = ((long long)blockIdx.x * THREADS + threadIdx.x) * 4;
+    if (g >= total) return;
+    int x0, x;
+    const uint32_t* row = gather_row(src, g, planes, H, W, S, nx, oy, ox, x0, x);
+    const uint32_t* s = row + x0 + x;
+    uint32_t* d = dst + g;
+    if (x + 4 <= S && x0 + x + 4 <= W && ((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d)) & 15) == 0) {
+        *reinterpret_cast<uint4*>(d) = *reinterpret_cast<const uint4*>(s);
+        return;
+    }
+    for (int j = 0; j < 4 && g + j < total; ++j) {
+        row = gather_row(src, g + j, planes, H, W, S, nx, oy, ox, x0, x);
+        d[j] = row[min(x0 + x, W - 1)];
     }
 }
 
@@ -207,6 +249,21 @@ extern "C" int evc_tile_gather_u8(const unsigned char* src, int N, int H, int W,
     else
         hipLaunchKernelGGL(tile_gather_kernel<1>, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, src, N, H, W, S, nx, oy, ox,
                            dst, total);
+    return hipGetLastError() == hipSuccess ? EVC_OK : EVC_ELAUNCH;
+}
+
+extern "C" int evc_tile_gather_f32(const float* src, int N, int C, int H, int W, int S, int ny, int nx, const int* oy_host,
+                                   const int* ox_host, const int* oy, const int* ox, float* dst, void* stream) {
+    if (!src || !dst || !oy || !ox || C <= 0 || C > SIDE || bad_grid(N, H, W, S, ny, nx, oy_host, ox_host, false)) return EVC_EINVAL;
+    const long long planes = (long long)N * C;                                  // below 2^48
+    if (planes > (1LL << 62) / H / W || planes > (1LL << 62) / S / S) return EVC_EINVAL;       // src and one tile's floats below 2^62
+    const long long per_tile = planes * S * S, tiles = (long long)ny * nx;
+    if (tiles > (1LL << 62) / per_tile) return EVC_EINVAL;
+    const long long total = tiles * per_tile;
+    unsigned blocks;
+    if (!blocks_of((total + 3) / 4, blocks)) return EVC_EINVAL;
+    hipLaunchKernelGGL(tile_gather_f32_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream,
+                       reinterpret_cast<const uint32_t*>(src), planes, H, W, S, nx, oy, ox, reinterpret_cast<uint32_t*>(dst), total);
     return hipGetLastError() == hipSuccess ? EVC_OK : EVC_ELAUNCH;
 }
 

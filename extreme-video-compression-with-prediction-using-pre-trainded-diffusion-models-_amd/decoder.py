@@ -38,6 +38,10 @@ class ClipDecoder:
         # the event demoted to the bf16 split (recovery.py); "off" (default, or EVC_RANGE_RECOVERY): the caller's
         # check_numerics stops the run.  Networks without event sites (UNetDDPM, pseudo-3-D) keep the "off" behaviour.
         self.range_recovery = recovery_mode(range_recovery)
+        if getattr(scorenet, "TILED", False) and self.range_recovery == "layer":
+            raise ValueError("joint generation over tiles (TiledScoreNet) does not combine with range recovery "
+                             "(range_recovery='layer'): recovery is not built for a network that runs a canvas as several "
+                             "launches per step; run with EVC_CONV_ARITH=bf16x6 (no range assumption) instead")
         if self.batch_invariant:
             self._refuse_recovery()
             self.invariant_net()           # fail now for a network without the mode
@@ -123,6 +127,10 @@ class ClipDecoder:
             # the SPADE network caches its per-chunk gamma / beta maps for ONE conditioning tensor: interleaved clip groups
             # would each pass their own slice and rebuild all maps on every forward (~20 ms against a 15 ms forward)
             groups = 1
+        if getattr(net, "TILED", False):
+            # the tiled view gathers the tiles of ONE conditioning tensor per chunk (tiled.py): per-group slices would be
+            # gathered again on every forward
+            groups = 1
         cond = cond_frames.reshape(B, -1, H, W).contiguous()
         if cfg.data.rescaled:
             cond = L.scale_clamp(cond, 2.0, -1.0)                          # data_transform: 2x - 1
@@ -177,11 +185,14 @@ class ClipDecoder:
         return self._stream_pool[:n]
 
     @torch.no_grad()
-    def decode(self, d, key_strings, shape, frames=30, noise_fn=None, generator=None, key_frames=None):
+    def decode(self, d, key_strings, shape, frames=30, noise_fn=None, generator=None, key_frames=None, size=None):
         """d: (frames,) 0/1 mask shared by the batch; key_strings: list over key-frame positions (in order) of
         ``[y_strings, z_strings]`` for the whole batch.  Returns (B, frames, 3, H, W) float32 on the device.
         ``key_frames``: the decoded key frames themselves, one (B, 3, H, W) device tensor per key-frame position, for a sender
-        that estimated its rate and has no strings (``ElicModel.estimate``); ``key_strings`` and ``shape`` are then not read."""
+        that estimated its rate and has no strings (``ElicModel.estimate``); ``key_strings`` and ``shape`` are then not read.
+        ``size`` = (H, W): the key frames are cropped to it before anything is generated from them (a whole-frame canvas whose
+        size is no multiple of the ELIC padding; default: they are used as decoded)."""
+        crop = (lambda x: x) if size is None else (lambda x: x[..., :size[0], :size[1]])
         d = np.asarray(d).reshape(-1)
         out = []
         k = 0
@@ -195,11 +206,11 @@ class ClipDecoder:
                 while t + run < frames and d[t + run] == 1:
                     run += 1
                 if key_frames is not None:
-                    out.append(torch.stack(list(key_frames[k:k + run]), 1))
+                    out.append(crop(torch.stack(list(key_frames[k:k + run]), 1)))
                     k += run
                     t += run
                     continue
-                x_hat = self.elic.decompress(KS.merge(key_strings[k:k + run]), shape)["x_hat"]      # (run*B, 3, H, W)
+                x_hat = crop(self.elic.decompress(KS.merge(key_strings[k:k + run]), shape)["x_hat"])      # (run*B, 3, H, W)
                 B = x_hat.shape[0] // run
                 x_hat = x_hat.reshape(run, B, *x_hat.shape[1:]).permute(1, 0, 2, 3, 4)
                 out.append(x_hat)
@@ -217,7 +228,7 @@ class ClipDecoder:
         return torch.cat(out, dim=1)[:, :frames].contiguous()
 
     @torch.no_grad()
-    def decode_jobs(self, jobs, max_batch=32, models=None, size=None, share=False, stats=None):
+    def decode_jobs(self, jobs, max_batch=32, models=None, size=None, share=False, stats=None, patch=64):
         """Decode policy-job streams (``container.unpack_job`` dicts; possibly different q, masks and program lengths).
 
         All jobs advance in lockstep, as ``policy.run_policy`` advances them on the sender: each round every unfinished job
@@ -229,7 +240,10 @@ class ClipDecoder:
         ("key", n) decode its n frames in one ``decompress`` call per q (several jobs share a call up to ``max_batch``
         frames; a segment is never split).  ``models``: q -> ElicModel (default: this decoder's own model for every q);
         ``size`` = (H, W) of a frame (default: the generator's image size): the ELIC output is cropped to it, as the sender
-        crops its padded frames.  The generator settings of the streams (sampler, subsample steps, denoise) must be the ones
+        crops its padded frames.  A stream whose hyper-latent ``shape`` is not that of a frame of ``size`` padded to ``patch``
+        (the sender's --patch; (ceil(H / 64), ceil(W / 64)) for the default 64) was made for frames of another size and is
+        refused (``StreamSizeError``, a ValueError) instead of being cropped to this one.
+        The generator settings of the streams (sampler, subsample steps, denoise) must be the ones
         this decoder was built with.  Format-4 jobs (``job["plan"]`` set: generated in batch-invariant mode) run their
         generation rounds on the network's batch-invariant view, in launches of their own: their frames are the sender's
         bit for bit at any ``max_batch``.
@@ -245,7 +259,7 @@ class ClipDecoder:
         either way.  ``stats``: optional dict; ``launch_sizes`` {samples in a launch: launches}, ``samples`` (generated samples),
         ``job_rounds`` (generation segments executed) and ``key_frames_decoded`` are added up in it.
         Returns one (frames, 3, H, W) float32 device tensor per job."""
-        run = _JobRounds(self, jobs, max_batch, models, size, share, stats)
+        run = _JobRounds(self, jobs, max_batch, models, size, share, stats, patch)
         run.check_jobs()
         while True:
             todo = [j for j in run.jobs if j.pos < len(j.stream["segments"])]
@@ -287,9 +301,9 @@ class _RxJob:
 class _JobRounds:
     """The steps of one ``ClipDecoder.decode_jobs`` call and what they share."""
 
-    def __init__(self, decoder, streams, max_batch, models, size, share, stats):
+    def __init__(self, decoder, streams, max_batch, models, size, share, stats, patch=64):
         cfg = decoder.config
-        self.decoder, self.max_batch, self.share, self.stats = decoder, max_batch, share, stats
+        self.decoder, self.max_batch, self.share, self.stats, self.patch = decoder, max_batch, share, stats, int(patch)
         self.jobs = [_RxJob(s) for s in streams]
         self.size = size if size is not None else (cfg.data.image_size, cfg.data.image_size)
         self.channels = cfg.data.channels * cfg.data.num_frames
@@ -312,6 +326,7 @@ class _JobRounds:
                 raise ValueError(f"job stream v{job['vid']} q{job['q']} thr {job['thr']:.2f} was generated with "
                                  f"{job['sampler']}-{job['subsample']} denoise={job['denoise']}: build the decoder with them")
             Cn.check_segments(job["segments"], job["frames"], len(job["key_strings"]))
+            check_stream_size(job, self.size, self.patch)
             if job.get("n_trials", 1) > 1:
                 Cn.check_trials(job["segments"], job["trials"], job["n_trials"])
 
@@ -381,6 +396,28 @@ class _JobRounds:
             self.count("key_frames_decoded", n)
             for j in part:
                 j.take_keys([next(x_hat) for _ in range(j.segment[1])])
+
+
+LATENT_STRIDE = 64             # frame samples per hyper-latent sample of ELIC (g_a: 16, h_a: 4)
+
+
+def latent_shape(size, patch=64):
+    """The hyper-latent shape of an (H, W) frame zero-padded to multiples of ``patch`` (``elic.pad_to_patch``)."""
+    return tuple(-(-int(n) // patch) * patch // LATENT_STRIDE for n in size)
+
+
+class StreamSizeError(ValueError):
+    """A job stream was made for frames of another size than the one it is decoded at."""
+
+
+def check_stream_size(job, size, patch=64):
+    """A job stream decodes at the frame size it was made for: its hyper-latent ``shape`` must be ``latent_shape(size)``."""
+    got, want = tuple(int(v) for v in job["shape"]), latent_shape(size, patch)
+    if got != want:
+        made = " x ".join(f"{(n - 1) * LATENT_STRIDE + 1}..{n * LATENT_STRIDE}" for n in got)
+        raise StreamSizeError(f"job stream v{job['vid']} q{job['q']} thr {job['thr']:.2f} was made for frames of {made} (rows x columns; "
+                              f"hyper-latent shape {got}), not for the {size[0]} x {size[1]} it is decoded at (shape {want}): pass "
+                              f"the sender's frame size")
 
 
 def total_bits(key_strings):

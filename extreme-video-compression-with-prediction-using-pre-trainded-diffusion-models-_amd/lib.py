@@ -200,6 +200,7 @@ HIP_SYMBOLS = {
     "evc_tile_grid_check": (c_int, [c_int] * 6 + [c_void_p, c_void_p, c_int]),
     "evc_tile_gather_u8": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 6),
     "evc_tile_blend_f32": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 6),
+    "evc_tile_gather_f32": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p] * 6),
     "evc_ssim_workspace_bytes": (c_longlong, [c_int, c_int, c_int]),
     "evc_ssim_planes_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_double, c_void_p, c_void_p,
                                     c_void_p]),
@@ -1451,6 +1452,29 @@ def tile_blend(tiles, H, W, oy, ox):
     _check(hip_lib().evc_tile_blend_f32(ptr(tiles), N, H, W, S, len(hy), len(hx), c_void_p(hy.ctypes.data), c_void_p(hx.ctypes.data),
                                         ptr(dy), ptr(dx), ptr(out), stream_ptr()), "evc_tile_blend_f32")
     return out
+
+
+def tile_gather_f32(x, S, oy, ox):
+    """x: (N, C, H, W) float32 on the device, any C -> (ny * nx, N, C, S, S) float32: ``tile_gather_u8`` for float planes, the
+    layout ``tests/tile_ref.py::gather`` defines.  A copy: NaN / inf pass through, nothing is clamped."""
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.is_cuda and x.is_contiguous(), \
+        "device-contiguous (N, C, H, W) float32 required"
+    N, C, H, W = x.shape
+    hy, hx, dy, dx = _tile_grid(N, H, W, int(S), oy, ox, x.device, False, "evc_tile_gather_f32")
+    out = torch.empty((len(hy) * len(hx), N, C, S, S), dtype=torch.float32, device=x.device)
+    _check(hip_lib().evc_tile_gather_f32(ptr(x), N, C, H, W, S, len(hy), len(hx), c_void_p(hy.ctypes.data), c_void_p(hx.ctypes.data),
+                                         ptr(dy), ptr(dx), ptr(out), stream_ptr()), "evc_tile_gather_f32")
+    return out
+
+
+def tile_blend_planes(tiles, H, W, oy, ox):
+    """tiles: (ny * nx, N, C, S, S) float32 with C a multiple of 3 -> (N, C, H, W) float32: ``tile_blend`` of the same memory
+    seen as (ny * nx, N * C / 3, 3, S, S) -- every plane is blended on its own, so the view changes no bit."""
+    if tiles.dim() != 5 or tiles.shape[2] % 3:
+        raise NotImplementedError(f"tile_blend_planes: tiles of shape {tuple(tiles.shape)}: (tiles, N, C, S, S) with C a multiple of 3 "
+                                  "is built (evc_tile_blend_f32 takes planes in threes)")
+    T, N, C, S, _ = tiles.shape
+    return tile_blend(tiles.view(T, N * C // 3, 3, S, S), H, W, oy, ox).view(N, C, int(H), int(W))
 
 
 def gate_residual(a, b, x, out=None):

@@ -13,6 +13,8 @@ was cut -- and the key of its noise (noise specification N1, DESIGN.md section 5
 decoded frames, in the same chunks, with the same noise as the sender judged.  The sampler, its step count and the denoise
 flag are read from the streams; only the ELIC models the streams name are loaded.  One process, one GPU.  With the original
 clips present each job's line carries its PSNR (``--ssim``, ``--lpips``: and those) and ``--fid`` adds a line, all from report.py.
+``--yuv-fit joint`` decodes the streams of a ``city_sender.py --yuv-fit joint`` run: whole frames of the size and tile grid that
+``canvas.json`` in ``--bitstream-dir`` names, generated jointly over the tiles (tiled.py); no source is needed.
 """
 import argparse
 import glob
@@ -57,11 +59,12 @@ def read_job_streams(directory):
     return out
 
 
-def decode_streams(blobs, net, cfg, model_for, max_batch=32, range_recovery=None, log=print, share=False, stats=None):
+def decode_streams(blobs, net, cfg, model_for, max_batch=32, range_recovery=None, log=print, share=False, stats=None, size=None):
     """blobs: [bytes]; model_for: q -> ElicModel (called once per q the streams name); -> ([job dict], [frames tensor]) in
     the order given.  A stream coded under another entropy arithmetic raises ``container.CodecMismatch``.  ``share`` and
     ``stats`` are ``ClipDecoder.decode_jobs``': decode every distinct key frame and generate every distinct state of a round
-    once, and count the samples generated."""
+    once, and count the samples generated.  ``size`` = (H, W) of a frame when it is not the generator's image size (``net`` is
+    then a ``tiled.TiledScoreNet``); a stream made for another size is refused (``ValueError``)."""
     import copy
     from . import lib as L, sampler as S
     from .decoder import ClipDecoder
@@ -83,7 +86,7 @@ def decode_streams(blobs, net, cfg, model_for, max_batch=32, range_recovery=None
         decoders.append(dec)
         idx = [i for i, j in enumerate(jobs) if (j["sampler"], j["subsample"], j["denoise"]) == setting]
         for i, f in zip(idx, dec.decode_jobs([jobs[i] for i in idx], max_batch=max_batch, models=models, share=share,
-                                                stats=stats)):
+                                                stats=stats, size=size)):
             frames[i] = f
     return jobs, frames, decoders
 
@@ -135,8 +138,9 @@ def build_parser():
 
 def main(argv=None):
     from . import cli, config as C, lib as L, report as R
-    args = cli.parse_args(argv, build_parser())
+    args = cli.parse_args(argv, build_parser(), receiver=True)
     R.check_metric_flags(args)
+    from .decoder import StreamSizeError
     from .elic import ElicModel
     from .scorenet import build_score_network
     paths = args.paths or cli.DEFAULT_PATHS
@@ -145,9 +149,28 @@ def main(argv=None):
         sys.exit(f"no job_*.evc under {args.bitstream_dir}")
     cfg, _ = C.load_config(args.config, args.config_mod)
     cfg.sampling.ckpt_id = args.ckpt or cfg.sampling.ckpt_id
+    canvas = None
+    if args.yuv_fit == "joint":      # whole frames generated jointly over tiles: the sender's canvas.json names size and grid
+        from . import video_io as V
+        try:
+            canvas = V.read_canvas(args.bitstream_dir)
+        except V.VideoFormatError as e:
+            sys.exit(f"--yuv-fit joint: {e}")
+        if canvas["size"] != cfg.data.image_size:
+            sys.exit(f"--yuv-fit joint: {os.path.join(args.bitstream_dir, V.CANVAS_NAME)} was written for a model of size "
+                     f"{canvas['size']}, config.data.image_size is {cfg.data.image_size}")
     device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cuda"
     L.hip_lib()
     net = build_score_network(cfg, cli.diffusion_weights(args, cfg), device=device)
+    size = None
+    if canvas is not None:
+        from .tiled import TiledScoreNet
+        try:
+            net = TiledScoreNet(net, canvas["size"], canvas["overlap"], tile_batch=max(1, args.batch))
+        except NotImplementedError as e:
+            sys.exit(f"--yuv-fit joint: {e}")
+        size = (canvas["height"], canvas["width"])
+        print(V.canvas_line(canvas["width"], canvas["height"], canvas["size"], canvas["overlap"], canvas["oy"], canvas["ox"]), flush=True)
     nets = R.load_networks(args, device)
     measurer = R.Measurer(ssim=args.ssim, fid_dims=args.fid_dims, **nets)
 
@@ -156,8 +179,12 @@ def main(argv=None):
 
     log = lambda m: print(m, flush=True)  # noqa: E731
     stats = {}
-    jobs, frames, decoders = decode_streams([b for _, b in streams], net, cfg, model_for, max_batch=max(1, args.batch),
-                                            range_recovery=args.range_recovery, log=log, share=args.share_generations, stats=stats)
+    try:
+        jobs, frames, decoders = decode_streams([b for _, b in streams], net, cfg, model_for, max_batch=max(1, args.batch),
+                                                range_recovery=args.range_recovery, log=log, share=args.share_generations,
+                                                stats=stats, size=size)
+    except StreamSizeError as e:
+        sys.exit(f"{e}" + ("" if canvas is not None else " (streams of a --yuv-fit joint sender: pass --yuv-fit joint)"))
     if args.share_generations:
         log(f"shared generations: {stats.get('samples', 0)} sample-rounds generated for {stats.get('job_rounds', 0)} job-rounds "
             f"served, {stats.get('key_frames_decoded', 0)} key frames decoded")

@@ -309,10 +309,25 @@ def tile_manifest(width, height, size, overlap, clips, frames, fps, source):
                 source=os.path.basename(str(source)))
 
 
-def write_manifest(directory, manifest):
+CANVAS_NAME = "canvas.json"        # --yuv-fit joint: the same fields for ONE video per clip, generated jointly over the grid (tiled.py)
+
+
+def canvas_line(width, height, size, overlap, oy, ox):
+    return f"{width}x{height} frames, joint generation over {len(oy)} x {len(ox)} tiles of {size}x{size} (overlap {overlap})"
+
+
+def read_canvas(directory):
+    """canvas.json of a ``--yuv-fit joint`` sender in ``directory`` -> its dict, checked as ``read_manifest`` checks."""
+    path = os.path.join(directory, CANVAS_NAME)
+    if not os.path.isfile(path):
+        raise VideoFormatError(f"{path}: no such file (the sender's --yuv-fit joint writes it beside the job streams)")
+    return read_manifest(path)
+
+
+def write_manifest(directory, manifest, name=MANIFEST_NAME):
     import json
     os.makedirs(directory, exist_ok=True)
-    path = os.path.join(directory, MANIFEST_NAME)
+    path = os.path.join(directory, name)
     with open(path, "w") as fh:
         json.dump(manifest, fh, indent=1, sort_keys=True)
         fh.write("\n")

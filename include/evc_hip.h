@@ -635,12 +635,23 @@ int evc_resample_v_u8(const unsigned char* src, int planes, int rows, int cols, 
  *                         The padding samples of an axis shorter than S are never read.  Nothing is clamped: a NaN / inf in a
  *                         tile reaches exactly the pixels that tile covers.  No atomics; one thread owns 4 adjacent pixels (one
  *                         16-byte store, W % 4 == 0) or one: a frame's bits depend on its own tiles and the grid only, not on
- *                         N, its place in the batch or the other frames. */
+ *                         N, its place in the batch or the other frames.  Tiles (T, N, C, S, S) with C % 3 == 0 are, bit for
+ *                         bit, the (T, N * C / 3, 3, S, S) this entry takes: planes are blended one by one.
+ *   evc_tile_gather_f32   the gather for fp32 planes of any channel count C (1 .. 2^24): src (N, C, H, W) -> dst (ny * nx, N, C,
+ *                         S, S), packed, by the same formula -- a copy of 32-bit words: NaN / inf pass through with their bits,
+ *                         nothing is clamped.  One kernel for every shape: a thread owns 4 consecutive destination floats and
+ *                         moves them as one 16-byte load and store where they lie in one tile row, their source columns lie
+ *                         inside the row and both addresses are 16-byte aligned; elsewhere (odd W, origins or S that are no
+ *                         multiples of 4, edge replication) float by float under the clamp.  No atomics; a sample's tiles do
+ *                         not depend on N.  (Joint generation, DESIGN.md section 8c: tiled.py gathers the noisy state and the
+ *                         conditioning frames of a canvas with it.) */
 int evc_tile_grid_check(int N, int H, int W, int S, int ny, int nx, const int* oy_host, const int* ox_host, int cover);
 int evc_tile_gather_u8(const unsigned char* src, int N, int H, int W, int S, int ny, int nx, const int* oy_host,
                        const int* ox_host, const int* oy, const int* ox, unsigned char* dst, void* stream);
 int evc_tile_blend_f32(const float* tiles, int N, int H, int W, int S, int ny, int nx, const int* oy_host, const int* ox_host,
                        const int* oy, const int* ox, float* out, void* stream);
+int evc_tile_gather_f32(const float* src, int N, int C, int H, int W, int S, int ny, int nx, const int* oy_host,
+                        const int* ox_host, const int* oy, const int* ox, float* dst, void* stream);
 
 /* ---- SSIM: the structural similarity of the reference's metric helpers (csrc/ssim.hip) ------
  * ssim() of fvd_utils/calculate_ssim.py:6-23 for N pairs of planes.  a, b: N contiguous planes of H x W fp32 each, values
