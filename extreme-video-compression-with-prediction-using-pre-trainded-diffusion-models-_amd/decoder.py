@@ -339,14 +339,11 @@ class _JobRounds:
             states = self.grouper.group(same, self.share, state=lambda j: (j.stream["stream_id"], len(j.x), j.trial, j.ids[-1], j.ids[-2]))
             self.count("job_rounds", len(same))
             self.count("samples", len(states))
-            for c0 in range(0, len(states), self.max_batch):
-                part = states[c0:c0 + self.max_batch]
+            for part in P.in_launches(states, self.max_batch):
                 heads = [members[0] for _, members in part]                              # a state's members hold the same frames
-                cond = torch.stack([torch.stack(j.x[-2:], 0) for j in heads], 0).contiguous()
                 noise = P.n1_noise([(j.stream["stream_id"], P.trial_start(len(j.x), j.trial)) for j in heads], seed, self.decoder.device)
-                pred = self.decoder.generate(cond, groups=1, invariant=inv, noise_fn=noise)
+                pred = P.generation_launch(self.decoder, heads, noise, inv, self.stats)
                 assert pred.shape[1] * pred.shape[2] == self.channels
-                P.count_launch(self.stats, len(part))
                 for k, (serial, members) in enumerate(part):
                     for j in members:                                                    # each keeps what its own segment names
                         n = j.segment[1]

@@ -30,6 +30,7 @@ city_sender.py:257-260).  ``CallableMetric`` is the hook for ``decide_5to5_lpips
 threshold): LPIPS needs torchvision's pretrained AlexNet, which cannot be fetched offline, so the metric is supplied
 by the user (``--policy lpips --metric pkg.module:function`` or the ``lpips`` package when it is importable).
 """
+import functools
 import importlib
 import os
 import time
@@ -242,6 +243,219 @@ def count_launch(stats, samples):
         h[samples] = h.get(samples, 0) + 1
 
 
+def in_launches(states, n):
+    """A round's states (or whatever rides one per sample) in their order, cut into launches of at most n."""
+    return [states[c0:c0 + n] for c0 in range(0, len(states), n)]
+
+
+def generation_launch(decoder, samples, noise_fn, invariant, stats):
+    """One generation launch, the sender's and the receiver's: ``samples`` holds one job per sample (anything with ``.x``; the sender
+    repeats a state's head once per noise trial), whose last two frames are the conditioning pair.  -> (n, 5, 3, H, W)."""
+    cond = torch.stack([torch.stack(j.x[-2:], 0) for j in samples], 0).contiguous()           # (n, 2, 3, H, W)
+    pred = decoder.generate(cond, noise_fn=noise_fn, groups=1, invariant=invariant)
+    count_launch(stats, len(samples))
+    return pred
+
+
+def torch_noise_seed(seed, sid, at, step):
+    """The generator seed of ``noise="torch"``: (20 bits of seed, stream id, 6 bits of round / start frame, 10 bits of step)."""
+    return ((((int(seed) & 0xFFFFF) << 20 | sid) << 6 | at) << 10 | step) & (2 ** 63 - 1)
+
+
+def timed_noise(stats, fn, tag, shape):
+    """``fn(tag, shape)``, its host time added to ``stats`` (launches are asynchronous: this is the CPU's share)."""
+    t0 = time.perf_counter()
+    out = fn(tag, shape)
+    stats["noise_host_seconds"] = stats.get("noise_host_seconds", 0.0) + time.perf_counter() - t0
+    return out
+
+
+class _Sweep:
+    """The steps of one ``run_policy`` call and what they share: the sender's side of ``decoder._JobRounds``."""
+
+    def __init__(self, decoder, models, clips, qs, thresholds, metric, *, patch, frames, max_batch, seed, bpp_limit, device, log,
+                 noise_source, stats, noise, batch_invariant, noise_streams, share, estimate, trials):
+        self.decoder, self.models, self.clips, self.qs, self.metric = decoder, models, clips, qs, metric
+        self.patch, self.frames, self.max_batch, self.seed, self.bpp_limit = patch, frames, max_batch, seed, bpp_limit
+        self.device, self.log, self.noise_source, self.stats, self.noise = device, log, noise_source, stats, noise
+        self.batch_invariant, self.noise_streams, self.share = batch_invariant, noise_streams, share
+        self.estimate, self.trials = estimate, trials
+        self.jobs, uid, gid = [], 0, 0
+        for vid in clips:
+            for q in qs:
+                for thr in thresholds:
+                    self.jobs.append(_Job(uid, vid, q, thr, sid=gid if noise_streams == "group" else None))
+                    uid += 1
+                gid += 1
+        self.key_cache = {}             # (vid, q, frame) -> (x_hat on device, bits, strings)
+        self.shapes = []                # hyper-latent shape of every ELIC call (all equal: one frame size)
+        self.grouper = StateGrouper()
+
+    def check(self):
+        """The combinations of settings that mean nothing are refused before any work."""
+        noise, noise_source, noise_streams = self.noise, self.noise_source, self.noise_streams
+        if noise not in ("torch", "evc"):
+            raise ValueError(f"noise must be 'torch' or 'evc', not {noise!r}")
+        if self.batch_invariant and noise != "evc":
+            raise ValueError("batch_invariant needs noise='evc': torch's generators are not replayable by a receiver, so there is "
+                             "nobody to reproduce the frames")
+        if noise_streams not in ("job", "group"):
+            raise ValueError(f"noise_streams must be 'job' or 'group', not {noise_streams!r}")
+        if noise_streams == "group" and noise_source is not None:
+            raise ValueError("noise_streams='group' does not combine with noise_source, which is keyed per (job, round)")
+        if self.share and noise_streams != "group":
+            raise ValueError("share=True needs noise_streams='group': jobs that draw from streams of their own never generate "
+                             "the same frames, so there is nothing to share")
+        self.trials = trials = int(self.trials)
+        if trials < 1:
+            raise ValueError(f"trials must be >= 1, not {trials}")
+        if trials > 1:
+            if noise != "evc" or noise_source is not None:
+                raise ValueError("trials > 1 needs noise='evc' and no noise_source: the receiver regenerates the chosen draw from the "
+                                 "trial number alone, which only the keyed noise of specification N1 allows")
+            if trials > self.max_batch:
+                raise ValueError(f"trials = {trials} > max_batch = {self.max_batch}: the trials of a state ride in one launch, and "
+                                 "max_batch counts samples")
+            if trials > MAX_TRIALS:
+                raise ValueError(f"trials = {trials} > {MAX_TRIALS}: a job stream names the trial in one byte")
+        if self.batch_invariant:
+            self.decoder._refuse_recovery()
+        if noise == "evc" and noise_source is None:
+            cfg = self.decoder.config
+            if getattr(cfg.model, "gamma", False):
+                raise NotImplementedError("noise='evc': noise specification N1 defines Gaussian noise only (config.model.gamma is set)")
+            if float(getattr(cfg.sampling, "t_min", -1) or -1) > 0:
+                raise NotImplementedError("noise='evc': noise specification N1 has no draw for a t_min > 0 start")
+
+    def start(self):
+        """The originals go to the device, and every job starts from its first two key frames (city_sender.py:521-524)."""
+        self.gt_dev = {vid: c.to(device=self.device, dtype=torch.float32) for vid, c in self.clips.items()}
+        self.size = next(iter(self.clips.values())).shape[-2:]
+        self.key_round(self.jobs)
+
+    def ensure_keys(self, wanted):
+        """Code every missing (vid, q, frame) of ``wanted``: one batched ELIC encode + decode per q."""
+        for q in self.qs:
+            todo = sorted({k for k in wanted if k[1] == q and k not in self.key_cache})
+            for part in in_launches(todo, self.max_batch):
+                x = torch.stack([self.gt_dev[v][f] for (v, _, f) in part], 0)
+                xh, bits, strings, shape = (estimated_batch if self.estimate else coded_batch)(self.models[q], x, self.patch)
+                self.shapes.append(tuple(shape))
+                for i, k in enumerate(part):
+                    self.key_cache[k] = (xh[i], bits[i], None if strings is None else strings[i])
+
+    def add_keys(self, job, fs):
+        """The coded frames ``fs`` become the job's next segment, ("key", len(fs))."""
+        for f in fs:
+            xh, b, st = self.key_cache[(job.vid, job.q, f)]
+            job.x.append(xh); job.bits.append(b); job.d.append(1); job.strings.append(st)
+            job.ids.append(key_id(job.vid, job.q, f))
+        if len(fs):
+            job.segments.append(("key", len(fs)))
+            job.trials.append(0)
+
+    def key_round(self, jobs):
+        """jobs: those that go on from key frames, in the order they were judged -- the next two frames of each (at the clip's end
+        the one that is left; frames 0 and 1 of a job that holds none).  Coded in one call for all of them, then added job by job."""
+        fs = [(0, 1) if not j.x else [f for f in (len(j.x), len(j.x) + 1) if f < self.frames] for j in jobs]
+        self.ensure_keys({(j.vid, j.q, f) for j, mine in zip(jobs, fs) for f in mine})
+        for j, mine in zip(jobs, fs):
+            self.add_keys(j, mine)
+
+    def drawn_noise(self, batch, tag, shape):
+        """``noise_source``'s or torch's noise for one launch: one counter-based stream per (job, round, step) -- per (group, start
+        frame, step) under group streams --: independent of the batch composition."""
+        step = 0 if tag == "init" else int(tag) + 1
+        out = torch.empty(shape, device=self.device, dtype=torch.float32)
+        for i, (j, _) in enumerate(batch):
+            if self.noise_source is not None:
+                out[i] = self.noise_source((j.vid, j.q, j.thr), j.round, step, tuple(shape[1:])).to(self.device)
+                continue
+            g = torch.Generator(device=self.device)
+            g.manual_seed(torch_noise_seed(self.seed, j.sid, len(j.x) if self.noise_streams == "group" else j.round, step))
+            out[i] = torch.randn(shape[1:], device=self.device, dtype=torch.float32, generator=g)
+        return out
+
+    def noise_for(self, batch):
+        """batch: per sample (job, noise trial) -> the ``noise_fn`` of its launch, timed when there are ``stats``."""
+        if self.noise == "evc" and self.noise_source is None:
+            fn = n1_noise([(j.sid, trial_start(len(j.x), t)) for j, t in batch], self.seed, self.device)
+        else:
+            fn = functools.partial(self.drawn_noise, batch)
+        return fn if self.stats is None else functools.partial(timed_noise, self.stats, fn)
+
+    def generation_round(self, states):
+        """states: [(serial, members)] of the round.  max_batch counts samples: a state's K trials share its launch, sample
+        k * K + t being state k under noise trial t.  -> the jobs that kept no frame, in the order they were judged."""
+        fallback = []
+        for part in in_launches(states, self.max_batch // self.trials):
+            batch = [(members[0], t) for _, members in part for t in range(self.trials)]      # a state's members hold the same frames
+            pred = generation_launch(self.decoder, [j for j, _ in batch], self.noise_for(batch),
+                                     True if self.batch_invariant else None, self.stats)
+            fallback += self.judge(pred, part)
+        return fallback
+
+    def judge(self, pred, part):
+        """One launch's candidates ``pred`` for the states ``part``: the metric of every candidate frame in one call, then each
+        member judges its state's [trial][frame] table by its own threshold.  -> the members that kept no frame."""
+        K, heads = self.trials, [members[0] for _, members in part]
+        n_new = [min(pred.shape[1], self.frames - len(j.x)) for j in heads]
+        flat_p = torch.cat([pred[k * K + t, :n] for k, n in enumerate(n_new) for t in range(K)], 0)
+        flat_g = torch.cat([self.gt_dev[j.vid][len(j.x):len(j.x) + n] for j, n in zip(heads, n_new) for t in range(K)], 0)
+        vals = self.metric.values(flat_p, flat_g)
+        fallback, o = [], 0
+        for k, (serial, members) in enumerate(part):
+            n = n_new[k]
+            table = [vals[o + t * n:o + (t + 1) * n] for t in range(K)]
+            o += n * K
+            fallback += [j for j in members if not self.take(j, serial, pred[k * K:(k + 1) * K], table)]
+        return fallback
+
+    def take(self, j, serial, cands, table):
+        """Job j keeps, of its state's candidates cands[trial][frame], the prefix ``choose_trial`` picks; -> the frames kept.  A
+        rejected round leaves no segment."""
+        trial, acc = choose_trial(table, j.thr, self.metric)
+        for t in range(acc):
+            j.x.append(cands[trial, t]); j.ids.append(gen_id(serial, t, trial)); j.d.append(0)
+        j.round += 1
+        if acc:
+            j.segments.append(("gen", acc))
+            j.trials.append(trial)
+        if self.trials > 1 and self.stats is not None:
+            self.stats.setdefault("trial_prefixes", []).append((tuple(accepted_prefixes(table, j.thr, self.metric)), trial))
+        return acc
+
+    def end_round(self, active, states, fallback):
+        """The round's statistics and its log line."""
+        stats = self.stats
+        if stats is not None:
+            stats["rounds"] = stats.get("rounds", 0) + 1
+            stats["key_frames_coded"] = len(self.key_cache)
+            stats.setdefault("states", []).append(len(states))
+            stats.setdefault("jobs_served", []).append(len(active))
+        if self.log is not None:
+            self.log(f"policy round: {len(active)} active jobs" + (f" in {len(states)} states" if self.share else "") +
+                     f", {len(fallback)} fell back to key frames")
+
+    def results(self):
+        """{(vid, q): [result dict per threshold]}, the thresholds of a (vid, q) cut at the first whose rate reaches ``bpp_limit``."""
+        (H, W), frames, out = self.size, self.frames, {}
+        for j in self.jobs:
+            lst = out.setdefault((j.vid, j.q), [])
+            if lst and lst[-1] is None:
+                continue                                            # sweep of this (vid, q) already cut
+            side = trial_bits(j.segments, self.trials)
+            bpp = (sum(j.bits) + side) / H / W / frames
+            if bpp >= self.bpp_limit:
+                lst.append(None)
+                continue
+            lst.append(dict(thr=j.thr, x=torch.stack(j.x[:frames], 0).cpu().numpy(), d=np.asarray(j.d[:frames], dtype=np.int64),
+                            bits=list(j.bits), bpp=bpp, segments=list(j.segments), stream_id=j.sid, seed=int(self.seed),
+                            key_strings=list(j.strings), shape=self.shapes[0], invariant=bool(self.batch_invariant),
+                            n_trials=self.trials, trials=list(j.trials), trial_bits=side))
+        return {k: [r for r in v if r is not None] for k, v in out.items()}
+
+
 def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=30, max_batch=32, seed=0,
                bpp_limit=1.0, device="cuda", log=None, noise_source=None, stats=None, noise="torch", batch_invariant=False,
                noise_streams="job", share=False, estimate=False, trials=1):
@@ -299,172 +513,20 @@ def run_policy(decoder, models, clips, qs, thresholds, metric, patch=64, frames=
     order: ("key", n) for n key frames decoded in one ELIC call (the initial pair, each fall-back pair, 1 at the clip's
     end), ("gen", n) for a round of which n >= 1 frames were kept (a rejected round leaves no frame and no entry: its noise
     key is never reused, because the fall-back moves the start frame on); ``key_strings`` the key frames' strings in order."""
-    if noise not in ("torch", "evc"):
-        raise ValueError(f"noise must be 'torch' or 'evc', not {noise!r}")
-    if batch_invariant and noise != "evc":
-        raise ValueError("batch_invariant needs noise='evc': torch's generators are not replayable by a receiver, so there is "
-                         "nobody to reproduce the frames")
-    if noise_streams not in ("job", "group"):
-        raise ValueError(f"noise_streams must be 'job' or 'group', not {noise_streams!r}")
-    if noise_streams == "group" and noise_source is not None:
-        raise ValueError("noise_streams='group' does not combine with noise_source, which is keyed per (job, round)")
-    if share and noise_streams != "group":
-        raise ValueError("share=True needs noise_streams='group': jobs that draw from streams of their own never generate "
-                         "the same frames, so there is nothing to share")
-    trials = int(trials)
-    if trials < 1:
-        raise ValueError(f"trials must be >= 1, not {trials}")
-    if trials > 1:
-        if noise != "evc" or noise_source is not None:
-            raise ValueError("trials > 1 needs noise='evc' and no noise_source: the receiver regenerates the chosen draw from the "
-                             "trial number alone, which only the keyed noise of specification N1 allows")
-        if trials > max_batch:
-            raise ValueError(f"trials = {trials} > max_batch = {max_batch}: the trials of a state ride in one launch, and "
-                             "max_batch counts samples")
-        if trials > MAX_TRIALS:
-            raise ValueError(f"trials = {trials} > {MAX_TRIALS}: a job stream names the trial in one byte")
-    if batch_invariant:
-        decoder._refuse_recovery()
-    if noise == "evc" and noise_source is None:
-        cfg = decoder.config
-        if getattr(cfg.model, "gamma", False):
-            raise NotImplementedError("noise='evc': noise specification N1 defines Gaussian noise only (config.model.gamma is set)")
-        if float(getattr(cfg.sampling, "t_min", -1) or -1) > 0:
-            raise NotImplementedError("noise='evc': noise specification N1 has no draw for a t_min > 0 start")
-    jobs, uid, gid = [], 0, 0
-    for vid in clips:
-        for q in qs:
-            for thr in thresholds:
-                jobs.append(_Job(uid, vid, q, thr, sid=gid if noise_streams == "group" else None))
-                uid += 1
-            gid += 1
-    gt_dev = {vid: c.to(device=device, dtype=torch.float32) for vid, c in clips.items()}
-    H, W = next(iter(clips.values())).shape[-2:]
-    key_cache = {}                  # (vid, q, frame) -> (x_hat on device, bits, strings)
-    shapes = []                     # hyper-latent shape of every ELIC call (all equal: one frame size)
-
-    def ensure_keys(wanted):
-        """Code every missing (vid, q, frame) of ``wanted``: one batched ELIC encode + decode per q."""
-        for q in qs:
-            todo = sorted({k for k in wanted if k[1] == q and k not in key_cache})
-            for c0 in range(0, len(todo), max_batch):
-                part = todo[c0:c0 + max_batch]
-                x = torch.stack([gt_dev[v][f] for (v, _, f) in part], 0)
-                xh, bits, strings, shape = (estimated_batch if estimate else coded_batch)(models[q], x, patch)
-                shapes.append(tuple(shape))
-                for i, k in enumerate(part):
-                    key_cache[k] = (xh[i], bits[i], None if strings is None else strings[i])
-
-    def add_keys(job, fs):
-        for f in fs:
-            xh, b, st = key_cache[(job.vid, job.q, f)]
-            job.x.append(xh); job.bits.append(b); job.d.append(1); job.strings.append(st)
-            job.ids.append(key_id(job.vid, job.q, f))
-        if len(fs):
-            job.segments.append(("key", len(fs)))
-            job.trials.append(0)
-
-    ensure_keys({(j.vid, j.q, f) for j in jobs for f in (0, 1)})          # city_sender.py:521-524
-    for j in jobs:
-        add_keys(j, (0, 1))
-
-    def _noise_for(batch):
-        if noise == "evc" and noise_source is None:
-            return n1_noise([(j.sid, trial_start(len(j.x), t)) for j, t in batch], seed, device)
-
-        def fn(tag, shape):      # one counter-based stream per (job, round, step) -- per (group, start frame, step) under group
-            # streams --: independent of the batch composition
-            step = 0 if tag == "init" else int(tag) + 1
-            out = torch.empty(shape, device=device, dtype=torch.float32)
-            if noise_source is not None:
-                for i, (j, _) in enumerate(batch):
-                    out[i] = noise_source((j.vid, j.q, j.thr), j.round, step, tuple(shape[1:])).to(device)
-                return out
-            for i, (j, _) in enumerate(batch):
-                g = torch.Generator(device=device)
-                at = len(j.x) if noise_streams == "group" else j.round
-                g.manual_seed(((((int(seed) & 0xFFFFF) << 20 | j.sid) << 6 | at) << 10 | step) & (2 ** 63 - 1))
-                out[i] = torch.randn(shape[1:], device=device, dtype=torch.float32, generator=g)
-            return out
-        return fn
-
-    def noise_for(batch):
-        fn = _noise_for(batch)
-        if stats is None:
-            return fn
-
-        def timed(tag, shape):       # host time spent drawing noise (launches are asynchronous: this is the CPU's share)
-            t0 = time.perf_counter()
-            out = fn(tag, shape)
-            stats["noise_host_seconds"] = stats.get("noise_host_seconds", 0.0) + time.perf_counter() - t0
-            return out
-        return timed
-
-    grouper = StateGrouper()
+    run = _Sweep(decoder, models, clips, qs, thresholds, metric, patch=patch, frames=frames, max_batch=max_batch, seed=seed,
+                 bpp_limit=bpp_limit, device=device, log=log, noise_source=noise_source, stats=stats, noise=noise,
+                 batch_invariant=batch_invariant, noise_streams=noise_streams, share=share, estimate=estimate, trials=trials)
+    run.check()
+    run.start()
     while True:
-        active = [j for j in jobs if len(j.x) < frames]
+        active = [j for j in run.jobs if len(j.x) < frames]
         if not active:
             break
-        states = grouper.group(active, share)            # [(serial, members)]: one generated sample per state
-        fallback = []
-        per_launch = max_batch // trials                 # max_batch counts samples: a state's K trials share its launch
-        for c0 in range(0, len(states), per_launch):
-            part = states[c0:c0 + per_launch]
-            heads = [members[0] for _, members in part]                                       # a state's members hold the same frames
-            batch = [(j, t) for j in heads for t in range(trials)]                            # sample k * K + t: state k, noise trial t
-            cond = torch.stack([torch.stack(j.x[-2:], 0) for j, _ in batch], 0).contiguous()  # (n, 2, 3, H, W)
-            pred = decoder.generate(cond, noise_fn=noise_for(batch), groups=1,              # (n, 5, 3, H, W)
-                                    invariant=True if batch_invariant else None)
-            count_launch(stats, len(batch))
-            n_new = [min(pred.shape[1], frames - len(j.x)) for j, _ in batch]
-            flat_p = torch.cat([pred[k, :n_new[k]] for k in range(len(batch))], 0)
-            flat_g = torch.cat([gt_dev[j.vid][len(j.x):len(j.x) + n_new[k]] for k, (j, _) in enumerate(batch)], 0)
-            vals = metric.values(flat_p, flat_g)                 # every candidate frame of the launch in one call
-            o = 0
-            for k, (serial, members) in enumerate(part):
-                n = n_new[k * trials]
-                table = [vals[o + t * n:o + (t + 1) * n] for t in range(trials)]          # [trial][frame]
-                for j in members:                                # each member judges the state's candidates by its own threshold
-                    trial, acc = choose_trial(table, j.thr, metric)
-                    for t in range(acc):
-                        j.x.append(pred[k * trials + trial, t]); j.ids.append(gen_id(serial, t, trial)); j.d.append(0)
-                    j.round += 1
-                    if acc:
-                        j.segments.append(("gen", acc))
-                        j.trials.append(trial)
-                    if acc == 0:
-                        fallback.append(j)
-                    if trials > 1 and stats is not None:
-                        stats.setdefault("trial_prefixes", []).append((tuple(accepted_prefixes(table, j.thr, metric)), trial))
-                o += n * trials
-        if fallback:                 # city_sender.py:538-548: key-code the next two frames
-            ensure_keys({(j.vid, j.q, f) for j in fallback for f in (len(j.x), len(j.x) + 1) if f < frames})
-            for j in fallback:
-                add_keys(j, [f for f in (len(j.x), len(j.x) + 1) if f < frames])
-        if stats is not None:
-            stats["rounds"] = stats.get("rounds", 0) + 1
-            stats["key_frames_coded"] = len(key_cache)
-            stats.setdefault("states", []).append(len(states))
-            stats.setdefault("jobs_served", []).append(len(active))
-        if log is not None:
-            log(f"policy round: {len(active)} active jobs" + (f" in {len(states)} states" if share else "") +
-                f", {len(fallback)} fell back to key frames")
-
-    out = {}
-    for j in jobs:
-        lst = out.setdefault((j.vid, j.q), [])
-        if lst and lst[-1] is None:
-            continue                                            # sweep of this (vid, q) already cut
-        side = trial_bits(j.segments, trials)
-        bpp = (sum(j.bits) + side) / H / W / frames
-        if bpp >= bpp_limit:
-            lst.append(None)
-            continue
-        lst.append(dict(thr=j.thr, x=torch.stack(j.x[:frames], 0).cpu().numpy(), d=np.asarray(j.d[:frames], dtype=np.int64),
-                        bits=list(j.bits), bpp=bpp, segments=list(j.segments), stream_id=j.sid, seed=int(seed),
-                        key_strings=list(j.strings), shape=shapes[0], invariant=bool(batch_invariant),
-                        n_trials=trials, trials=list(j.trials), trial_bits=side))
-    return {k: [r for r in v if r is not None] for k, v in out.items()}
+        states = run.grouper.group(active, share)            # [(serial, members)]: one generated sample per state and trial
+        fallback = run.generation_round(states)
+        run.key_round(fallback)                              # city_sender.py:538-548: key-code the next two frames
+        run.end_round(active, states, fallback)
+    return run.results()
 
 
 def rd_envelope(bpp, metric_mean, higher_is_better):
