@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "build")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
-HIP_SOURCES = ["conv_igemm.hip", "attention.hip", "norm.hip", "fir.hip", "elementwise.hip", "gdn.hip", "stride2.hip", "lpips.hip", "i3d.hip", "frames.hip", "noise.hip", "yuv.hip", "rate.hip", "ssim.hip", "metric.hip", "inception.hip", "resample.hip", "tile.hip", "api.hip"]
+HIP_SOURCES = ["conv_igemm.hip", "nin_gemm.hip", "attention.hip", "norm.hip", "fir.hip", "elementwise.hip", "gdn.hip", "stride2.hip", "lpips.hip", "i3d.hip", "frames.hip", "noise.hip", "yuv.hip", "rate.hip", "ssim.hip", "metric.hip", "inception.hip", "resample.hip", "tile.hip", "api.hip"]
 ARCH = "gfx950"
 
 
@@ -45,6 +45,7 @@ def build(force=False, verbose=False):
     os.makedirs(LIBDIR, exist_ok=True)
     os.makedirs(OBJDIR, exist_ok=True)
     headers = [os.path.join(INCLUDE, h) for h in ("evc_hip.h", "evc_rans.h")]
+    headers += [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")]     # shared device helpers
     hipcc = hipcc_path()
     flags = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE]
     flags += os.environ.get("EVC_HIPCC_FLAGS", "").split()     # e.g. -DEVC_CONV_PC=1 for A/B experiments

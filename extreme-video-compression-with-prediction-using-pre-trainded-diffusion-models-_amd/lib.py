@@ -79,6 +79,19 @@ class ConvPlan(ctypes.Structure):
                 ("stats_runs", c_int), ("fused_1x1", c_int)]
 
 
+class NinArgs(ctypes.Structure):
+    """Mirror of ``evc_nin_args`` (include/evc_hip.h)."""
+    _fields_ = [("x", c_void_p), ("x1", c_void_p), ("Ci", c_int), ("Co", c_int), ("coef_a", c_void_p), ("coef_s", c_void_p),
+                ("in_bound", c_void_p), ("w_packed", c_void_p), ("arith", c_int), ("bias", c_void_p), ("res", c_void_p),
+                ("out_scale", c_float), ("act_out", c_int), ("out", c_void_p), ("stats_out", c_void_p),
+                ("B", c_int), ("H", c_int), ("W", c_int), ("tile", c_int)]
+
+
+class NinPlan(ctypes.Structure):
+    """Mirror of ``evc_nin_plan`` (include/evc_hip.h): what ``evc_nin_gemm_plan_query`` reports."""
+    _fields_ = [("kernel", ctypes.c_char * 64), ("tile_m", c_int), ("tile_n", c_int), ("stages", c_int), ("stats_runs", c_int)]
+
+
 class AttentionPlan(ctypes.Structure):
     """Mirror of ``evc_attention_plan`` (include/evc_hip.h): what ``evc_attention_plan_query`` reports."""
     _fields_ = [("kernel", ctypes.c_char * 64), ("waves", c_int), ("kparts", c_int), ("tiles_per_part", c_int),
@@ -164,6 +177,9 @@ HIP_SYMBOLS = {
     "evc_conv_workspace_bytes": (c_longlong, [POINTER(ConvArgs)]),
     "evc_conv2d_nhwc_f32": (c_int, [POINTER(ConvArgs), c_void_p, c_void_p]),
     "evc_conv2d_nhwc_profiled_f32": (c_int, [POINTER(ConvArgs), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "evc_nin_gemm_supported": (c_int, [POINTER(NinArgs)]),
+    "evc_nin_gemm_plan_query": (c_int, [POINTER(NinArgs), POINTER(NinPlan)]),
+    "evc_nin_gemm_f32": (c_int, [POINTER(NinArgs), c_void_p]),
     "evc_attention_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_float, c_void_p]),
     "evc_attention_workspace_bytes": (c_longlong, [c_int, c_int, c_int, c_int]),
@@ -983,6 +999,67 @@ def conv_workspace_bytes(B, H, W, Ci, Co, KH, KW, splits=0, arith=None):
     tail splits x tail rows when only the last partial round of tiles is split (C query, no launch)."""
     a = conv_query_args(B, H, W, Ci, 0, Co, KH, KW, default_arith() if arith is None else arith, splits=splits)
     return hip_lib(require_device=False).evc_conv_workspace_bytes(ctypes.byref(a))
+
+
+# ---- NIN projections of the attention blocks as a plain GEMM (csrc/nin_gemm.hip): a separate operation, not a convolution
+# plan -- ``conv2d_nhwc`` never launches it.  A caller asks ``nin_gemm_supported`` and keeps ``conv2d_nhwc`` where it says no.
+# Optional launch log: when a list is installed here every ``nin_gemm`` call appends its shape and plan.
+NIN_PROFILE = None
+
+
+def nin_query_args(B, H, W, Ci, Co, arith=ARITH_F16X3, coef=False, bound=None, two_sources=False, act_out=ACT_NONE, tile=0):
+    """``NinArgs`` for the queries below (no launch, works without a GPU): they read shapes and which pointers are set, never
+    memory, so every pointer is a non-null dummy.  ``bound`` defaults to the raw form when there are no coefficients."""
+    d = c_void_p(16)
+    bound = (not coef) if bound is None else bound
+    return NinArgs(x=d, x1=d if two_sources else None, Ci=Ci, Co=Co, coef_a=d if coef else None, coef_s=d if coef else None,
+                   in_bound=d if bound else None, w_packed=d, arith=arith, out_scale=1.0, act_out=act_out, out=d,
+                   B=B, H=H, W=W, tile=tile)
+
+
+def nin_gemm_supported(B, H, W, Ci, Co, arith=ARITH_F16X3, coef=False, **kw):
+    """Whether ``nin_gemm`` takes this projection (``evc_nin_gemm_supported``; works without a GPU)."""
+    a = nin_query_args(B, H, W, Ci, Co, arith, coef, **kw)
+    return bool(hip_lib(require_device=False).evc_nin_gemm_supported(ctypes.byref(a)))
+
+
+def nin_gemm_plan(B, H, W, Ci, Co, arith=ARITH_F16X3, coef=False, **kw):
+    """The launch's plan (``evc_nin_gemm_plan_query``; works without a GPU): kernel instance, tile, K stages, moment runs."""
+    out = NinPlan()
+    a = nin_query_args(B, H, W, Ci, Co, arith, coef, **kw)
+    _check(hip_lib(require_device=False).evc_nin_gemm_plan_query(ctypes.byref(a), ctypes.byref(out)), "evc_nin_gemm_plan_query")
+    return dict(kernel=out.kernel.decode(), tile=(out.tile_m, out.tile_n), stages=out.stages, stats_runs=out.stats_runs)
+
+
+def nin_gemm(x, w_packed, Co, bias=None, coef=None, res=None, out_scale=1.0, in_bound=None, want_stats=False, out=None,
+             tile=0):
+    """out = ((T(x) @ w^T) + bias + res) * out_scale on dense NHWC tensors: the 1x1 convolution of an attention block's
+    projection as one GEMM launch without K split (include/evc_hip.h).  T(x) = x * a + s with ``coef = (a, s)`` (an affine
+    GroupNorm), or x scaled from the element bound word ``in_bound``.  ``w_packed``: the F16X3 pack ``conv2d_nhwc`` takes for
+    the same filter.  ``want_stats=True`` returns ``(out, stats)`` with the moments of ``out`` in ``chan_stats`` layout.
+    Raises where ``nin_gemm_supported`` says no: there is no fallback here."""
+    L = hip_lib()
+    B, H, W, Ci = x.shape
+    assert x.is_contiguous() and x.dtype == torch.float32 and (res is None or (res.is_contiguous() and res.shape == (B, H, W, Co)))
+    if out is None:
+        out = torch.empty((B, H, W, Co), device=x.device, dtype=torch.float32)
+    assert out.is_contiguous() and out.shape == (B, H, W, Co)
+    ca, cs = coef if coef is not None else (None, None)
+    assert ca is None or (ca.shape == (B, Ci) and cs.shape == (B, Ci) and ca.is_contiguous() and cs.is_contiguous())
+    a = NinArgs(x=ptr(x), x1=None, Ci=Ci, Co=Co, coef_a=ptr(ca), coef_s=ptr(cs), in_bound=_word(in_bound),
+                w_packed=ptr(w_packed), arith=packed_arith(w_packed), bias=ptr(bias), res=ptr(res), out_scale=float(out_scale),
+                act_out=ACT_NONE, out=ptr(out), B=B, H=H, W=W, tile=tile)
+    plan = NinPlan()
+    _check(L.evc_nin_gemm_plan_query(ctypes.byref(a), ctypes.byref(plan)), "evc_nin_gemm_plan_query")
+    stats = None
+    if want_stats:
+        stats = torch.empty((B, plan.stats_runs, Co, 2), device=x.device, dtype=torch.float32)
+        a.stats_out = ptr(stats)
+    _check(L.evc_nin_gemm_f32(ctypes.byref(a), stream_ptr()), "evc_nin_gemm_f32")
+    if NIN_PROFILE is not None:
+        NIN_PROFILE.append(dict(kernel=plan.kernel.decode(), tile=(plan.tile_m, plan.tile_n), shape=(B, H, W, Ci, Co),
+                                coef=coef is not None, bound=in_bound is not None, res=res is not None, stats=bool(want_stats)))
+    return (out, stats) if want_stats else out
 
 
 def attention_set_option(name, value):

@@ -646,17 +646,36 @@ class ScoreNet(DdpmWrapper):
         qkvb = self._bound_slot(3)
         if qkvb is None:
             obound = None
-            qkv = self._conv(x.t, e["wqkv"], 3 * C, 1, 1, bias=e["bqkv"], coef=coef)
+            qkv = self._proj(x.t, e["wqkv"], 3 * C, e["bqkv"], coef=coef)
         else:
             # element bounds of q, k, v from the projection's fused moments (one small launch); the attention output is
             # a convex combination of value rows, so max |o| <= max |v|: v's bound also serves the output projection
-            qkv, qst = self._conv(x.t, e["wqkv"], 3 * C, 1, 1, bias=e["bqkv"], coef=coef, want_stats=True)
+            qkv, qst = self._proj(x.t, e["wqkv"], 3 * C, e["bqkv"], coef=coef, want_stats=True)
             self._mbound(qst, 0, C, qkvb, site=self._site("attn_qkv", i))
             # v's bound: one word, or in batch-invariant mode every sample's third word gathered into B consecutive ones
             obound = _f16_only(e["wo"], qkvb.view(B, 3)[:, 2].contiguous() if self.batch_invariant else qkvb[2:3])
         o = self._attention(qkv.view(B, H * W, 3 * C), C, heads, bounds=None if i in self._attn_f32 else qkvb)
-        return self._act(*self._conv(o.view(B, H, W, C), e["wo"], C, 1, 1, bias=e["bo"], res=x.t,
-                                   out_scale=INV_SQRT2, want_stats=True, in_bound=obound))
+        return self._act(*self._proj(o.view(B, H, W, C), e["wo"], C, e["bo"], res=x.t, out_scale=INV_SQRT2, want_stats=True,
+                                     in_bound=obound))
+
+    # The attention blocks' projections (q | k | v, output + residual) on the no-split GEMM kernel (lib.nin_gemm) instead of the
+    # 1x1 convolution.  A plain attribute, on by default: ``net.nin_gemm = False`` between two forwards of one process puts
+    # them back on the convolution (tools/ab_forward.py alternates it).  (Defined below _attn: tests/attention_ledger.py pins
+    # the line of its attention call.)
+    nin_gemm = True
+
+    def _proj(self, x, w, Co, bias, coef=None, res=None, out_scale=1.0, want_stats=False, in_bound=None):
+        """A projection (NIN) of an attention block: the no-split GEMM where it applies, else the 1x1 convolution as before.
+        Batch-invariant networks, the SPADE and 3-D networks, demoted sites (repacked to bf16x6) and shapes the GEMM does not
+        take keep the convolution."""
+        B, H, W, Ci = x.shape
+        plain = not self.batch_invariant and not self.SPADE and self.ARCH == "unetmore"      # the other networks keep the convolution
+        if self.nin_gemm and plain and L.packed_arith(w) == L.ARITH_F16X3 and \
+                L.nin_gemm_supported(B, H, W, Ci, Co, coef=coef is not None, bound=in_bound is not None):
+            return L.nin_gemm(x, w, Co, bias=bias, coef=coef, res=res, out_scale=out_scale, in_bound=in_bound,
+                              want_stats=want_stats)
+        return self._conv(x, w, Co, 1, 1, bias=bias, coef=coef, res=res, out_scale=out_scale, want_stats=want_stats,
+                          in_bound=in_bound)
 
     @torch.no_grad()
     def forward_rows(self, x, rows, cond=None):

@@ -300,6 +300,49 @@ int evc_attention_invariant_f32(const float* q, const float* k, const float* v, 
  * kernel's own duration, the figure rocprofv3 --kernel-trace reports for it (bench.py's roofline leg). */
 int evc_conv2d_nhwc_profiled_f32(const evc_conv_args* a, float* ws, void* stream, void* ev_start, void* ev_conv_end);
 
+/* ---- NIN / linear projection as a plain GEMM (attention blocks) ------------------------------
+ * The 1x1 convolutions of an attention block (q | k | v, and the output projection with its residual) as ONE launch with
+ * no K split, no workspace and no second kernel: every output element and every moment entry has one writer and a fixed
+ * summation order, so the result does not depend on the grid.  EVC_ARITH_F16X3 only, on the SAME packed weights as
+ * evc_conv2d_nhwc_f32 takes for the 1x1 filter (header + [Ci/16][2 planes][CoPad][16] fp16), and to the bit the arithmetic
+ * of that convolution's unsplit kernel:
+ *     out[m][n] = ((sum_k T(x[m][k]) * w[n][k]) + bias[n] + res[m][n]) * out_scale
+ *   T(x) = x * coef_a[b][k] + coef_s[b][k]   (coef_a and coef_s set, in_bound NULL: an affine GroupNorm, operand scale 8), or
+ *   T(x) = x                                 (coef_* NULL, in_bound set: a raw operand scaled from its element bound word).
+ * x, res, out are dense [B*H*W][Ci / Co / Co].  stats_out (optional): moments of `out`, [B][stats_runs][Co][2] in the
+ * layout of evc_chan_stats_f32, stats_runs from evc_nin_gemm_plan_query.  Nothing is clamped: a NaN / inf operand element
+ * makes its pixel's output row non-finite, the NaN pattern in the bound word makes the whole output NaN.
+ * This is a separate operation: evc_conv2d_nhwc_f32 never launches it and the convolution's plan queries do not know it.
+ * A caller asks evc_nin_gemm_supported first and keeps the convolution where it says 0; the launch does not fall back. */
+typedef struct {
+    const float* x; const float* x1;      /* x1: a second source -- not supported, must be NULL */
+    int Ci; int Co;
+    const float* coef_a; const float* coef_s;
+    const unsigned* in_bound;
+    const float* w_packed; int arith;     /* EVC_ARITH_*: the packing of w_packed */
+    const float* bias; const float* res;
+    float out_scale; int act_out;         /* act_out: EVC_ACT_NONE is the only one supported */
+    float* out; float* stats_out;
+    int B; int H; int W;
+    int tile;                             /* 0 = choose (every caller but an A/B measurement); 22 / 21 / 11 force the 128 x 128 /
+                                             128 x 64 / 64 x 64 pixel x channel tile (unsupported where it does not divide) */
+} evc_nin_args;
+/* The launch's plan: kernel instance as rocprofv3 --kernel-trace prints it, pixel x channel tile (a pure function of
+ * B*H*W, Ci, Co and H*W), K stages of 64 channels, pixel runs per image of the fused moments. */
+typedef struct {
+    char kernel[64];
+    int tile_m, tile_n, stages, stats_runs;
+} evc_nin_plan;
+/* 1 when the launch takes these arguments: an F16X3 pack, a single source, Ci % 64 == 0, Co % 64 == 0, H*W a multiple of the
+ * shape's pixel tile, one of the two on-load forms, no output activation -- and (tile == 0 only) the grid is not one the
+ * convolution serves better: Co % 192 == 0, H*W % 128 == 0 and at least 256 tiles of 128 pixels x 192 channels, which its
+ * unsplit kernel fills the chip with (measured: profiles/NOTES.md).  Reads shapes and which pointers are set, never
+ * memory; needs no device.  Everything else gets EVC_EUNSUPPORTED from the launch and the plan query (EVC_EINVAL for a
+ * NULL x / w_packed / out or a size <= 0). */
+int evc_nin_gemm_supported(const evc_nin_args* a);
+int evc_nin_gemm_plan_query(const evc_nin_args* a, evc_nin_plan* out);
+int evc_nin_gemm_f32(const evc_nin_args* a, void* stream);
+
 /* ---- multi-head spatial self-attention ------------------------------------------------------
  * out[b][n][h*D + d] = sum_m softmax_m(q[b][n][h].k[b][m][h] * scale) * v[b][m][h][d]
  * q, k, v: [B][N][ld_*] token-major with head h at channel offset h*D; D in {32, 64, 128, 192, 256}

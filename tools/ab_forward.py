@@ -1,5 +1,7 @@
 """Forward-level same-process A/B of a convolution dispatch option (default: "wide256", the 256 x 192 one-workgroup-per-CU
-kernel) or of an attention option ("short_seq", "kv_planes"): alternating rounds of whole score-network forwards at the benchmark batch size, HIP-event timed.
+kernel) or of an attention option ("short_seq", "kv_planes"), or of the network's ``nin_gemm`` attribute (the attention
+projections on the no-split GEMM kernel): alternating rounds of whole score-network forwards at the benchmark batch size,
+HIP-event timed.
 
     python tools/ab_forward.py [B] [option] [rounds] [forwards per round]
 """
@@ -24,7 +26,10 @@ x, c = torch.randn(B, 15, 128, 128, device="cuda"), torch.randn(B, 6, 128, 128, 
 outs = {}
 for r in range(rounds):
     for v in (0, 1):
-        (L.attention_set_option if opt in ("short_seq", "kv_planes") else L.conv_set_option)(opt, v)
+        if opt == "nin_gemm":
+            net.nin_gemm = bool(v)
+        else:
+            (L.attention_set_option if opt in ("short_seq", "kv_planes") else L.conv_set_option)(opt, v)
         for _ in range(2):
             o = net.forward_label(x, 500, c)
         torch.cuda.synchronize()
