@@ -92,6 +92,22 @@ class NinPlan(ctypes.Structure):
     _fields_ = [("kernel", ctypes.c_char * 64), ("tile_m", c_int), ("tile_n", c_int), ("stages", c_int), ("stats_runs", c_int)]
 
 
+class SmallConvArgs(ctypes.Structure):
+    """Mirror of ``evc_small_conv_args`` (include/evc_hip.h)."""
+    _fields_ = [("src0", c_void_p), ("src1", c_void_p), ("C0", c_int), ("C1", c_int),
+                ("coef_a", c_void_p), ("coef_s", c_void_p), ("act_in", c_int), ("in_bound", c_void_p),
+                ("w_packed", c_void_p), ("arith", c_int), ("bias", c_void_p), ("res", c_void_p),
+                ("out_scale", c_float), ("act_out", c_int), ("out", c_void_p), ("stats_out", c_void_p),
+                ("B", c_int), ("H", c_int), ("W", c_int), ("Co", c_int), ("KH", c_int), ("KW", c_int),
+                ("x2_w_packed", c_void_p), ("invariant", c_int), ("variant", c_int)]
+
+
+class SmallConvPlan(ctypes.Structure):
+    """Mirror of ``evc_small_conv_plan`` (include/evc_hip.h): what ``evc_small_conv_plan_query`` reports."""
+    _fields_ = [("kernel", ctypes.c_char * 64), ("variant", c_int), ("tile_m", c_int), ("tile_n", c_int), ("groups", c_int),
+                ("chunks", c_int), ("rounds", c_int), ("stats_runs", c_int)]
+
+
 class AttentionPlan(ctypes.Structure):
     """Mirror of ``evc_attention_plan`` (include/evc_hip.h): what ``evc_attention_plan_query`` reports."""
     _fields_ = [("kernel", ctypes.c_char * 64), ("waves", c_int), ("kparts", c_int), ("tiles_per_part", c_int),
@@ -180,6 +196,9 @@ HIP_SYMBOLS = {
     "evc_nin_gemm_supported": (c_int, [POINTER(NinArgs)]),
     "evc_nin_gemm_plan_query": (c_int, [POINTER(NinArgs), POINTER(NinPlan)]),
     "evc_nin_gemm_f32": (c_int, [POINTER(NinArgs), c_void_p]),
+    "evc_small_conv_supported": (c_int, [POINTER(SmallConvArgs)]),
+    "evc_small_conv_plan_query": (c_int, [POINTER(SmallConvArgs), POINTER(SmallConvPlan)]),
+    "evc_small_conv_f32": (c_int, [POINTER(SmallConvArgs), c_void_p]),
     "evc_attention_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_float, c_void_p]),
     "evc_attention_workspace_bytes": (c_longlong, [c_int, c_int, c_int, c_int]),
@@ -1059,6 +1078,75 @@ def nin_gemm(x, w_packed, Co, bias=None, coef=None, res=None, out_scale=1.0, in_
     if NIN_PROFILE is not None:
         NIN_PROFILE.append(dict(kernel=plan.kernel.decode(), tile=(plan.tile_m, plan.tile_n), shape=(B, H, W, Ci, Co),
                                 coef=coef is not None, bound=in_bound is not None, res=res is not None, stats=bool(want_stats)))
+    return (out, stats) if want_stats else out
+
+
+# ---- 3x3 convolutions of the 16 x 16 / 8 x 8 levels with the K groups inside the workgroup (csrc/conv_small.hip): a separate
+# operation like ``nin_gemm`` -- ``conv2d_nhwc`` never launches it, a caller asks ``small_conv_supported`` and keeps
+# ``conv2d_nhwc`` where it says no.  Optional launch log: every ``small_conv`` call appends its shape and plan.
+SMALL_CONV_PROFILE = None
+
+
+def small_conv_query_args(B, H, W, C0, C1, Co, K=3, arith=ARITH_F16X3, coef=False, act_in=None, bound=False, act_out=ACT_NONE,
+                          x2=False, invariant=False, variant=0):
+    """``SmallConvArgs`` for the queries below (no launch, works without a GPU): they read shapes and which pointers are set,
+    never memory, so every pointer is a non-null dummy.  ``act_in`` defaults to the form's own (SiLU with coefficients)."""
+    d = c_void_p(16)
+    act_in = (ACT_SILU if coef else ACT_NONE) if act_in is None else act_in
+    return SmallConvArgs(src0=d, src1=d if C1 else None, C0=C0, C1=C1, coef_a=d if coef else None, coef_s=d if coef else None,
+                         act_in=act_in, in_bound=d if bound else None, w_packed=d, arith=arith, out_scale=1.0, act_out=act_out,
+                         out=d, B=B, H=H, W=W, Co=Co, KH=K, KW=K, x2_w_packed=d if x2 else None, invariant=int(bool(invariant)),
+                         variant=variant)
+
+
+def small_conv_supported(B, H, W, C0, C1, Co, **kw):
+    """Whether ``small_conv`` takes this convolution (``evc_small_conv_supported``; works without a GPU)."""
+    a = small_conv_query_args(B, H, W, C0, C1, Co, **kw)
+    return bool(hip_lib(require_device=False).evc_small_conv_supported(ctypes.byref(a)))
+
+
+def small_conv_plan(B, H, W, C0, C1, Co, **kw):
+    """The launch's plan (``evc_small_conv_plan_query``; works without a GPU): kernel instance and its number, tile, K groups,
+    chunks, rounds (chunks of the longest group), moment runs."""
+    out = SmallConvPlan()
+    a = small_conv_query_args(B, H, W, C0, C1, Co, **kw)
+    _check(hip_lib(require_device=False).evc_small_conv_plan_query(ctypes.byref(a), ctypes.byref(out)), "evc_small_conv_plan_query")
+    return dict(kernel=out.kernel.decode(), variant=out.variant, tile=(out.tile_m, out.tile_n), groups=out.groups,
+                chunks=out.chunks, rounds=out.rounds, stats_runs=out.stats_runs)
+
+
+def small_conv(src0, w_packed, Co, bias=None, src1=None, coef=None, act_in=ACT_NONE, res=None, out_scale=1.0, in_bound=None,
+               want_stats=False, out=None, variant=0):
+    """out = (conv3x3(T(cat[src0, src1]), w) + bias + res) * out_scale on dense NHWC tensors with H = W in {8, 16}: one launch,
+    the K range divided over wave groups inside each workgroup (include/evc_hip.h).  T = SiLU of the GroupNorm affine with
+    ``coef = (a, s)`` and ``act_in=ACT_SILU``, or nothing; ``in_bound``: the sources' element bound word (optional).
+    ``w_packed``: the F16X3 pack ``conv2d_nhwc`` takes for the same filter.  ``want_stats=True`` returns ``(out, stats)`` with
+    the moments of ``out`` in ``chan_stats`` layout.  Raises where ``small_conv_supported`` says no: there is no fallback."""
+    L = hip_lib()
+    B, H, W, C0 = src0.shape
+    C1 = 0 if src1 is None else src1.shape[-1]
+    for t, c in ((src0, C0), (src1, C1), (res, Co)):
+        assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.shape == (B, H, W, c))
+    if out is None:
+        out = torch.empty((B, H, W, Co), device=src0.device, dtype=torch.float32)
+    assert out.is_contiguous() and out.shape == (B, H, W, Co)
+    ca, cs = coef if coef is not None else (None, None)
+    assert ca is None or (ca.shape == (B, C0 + C1) and cs.shape == (B, C0 + C1) and ca.is_contiguous() and cs.is_contiguous())
+    a = SmallConvArgs(src0=ptr(src0), src1=ptr(src1), C0=C0, C1=C1, coef_a=ptr(ca), coef_s=ptr(cs), act_in=act_in,
+                      in_bound=_word(in_bound), w_packed=ptr(w_packed), arith=packed_arith(w_packed), bias=ptr(bias),
+                      res=ptr(res), out_scale=float(out_scale), act_out=ACT_NONE, out=ptr(out), B=B, H=H, W=W, Co=Co, KH=3, KW=3,
+                      variant=variant)
+    plan = SmallConvPlan()
+    _check(L.evc_small_conv_plan_query(ctypes.byref(a), ctypes.byref(plan)), "evc_small_conv_plan_query")
+    stats = None
+    if want_stats:
+        stats = torch.empty((B, plan.stats_runs, Co, 2), device=src0.device, dtype=torch.float32)
+        a.stats_out = ptr(stats)
+    _check(L.evc_small_conv_f32(ctypes.byref(a), stream_ptr()), "evc_small_conv_f32")
+    if SMALL_CONV_PROFILE is not None:
+        SMALL_CONV_PROFILE.append(dict(kernel=plan.kernel.decode(), tile=(plan.tile_m, plan.tile_n), groups=plan.groups,
+                                       shape=(B, H, W, C0 + C1, Co), C1=C1, coef=coef is not None, bound=in_bound is not None,
+                                       res=res is not None, stats=bool(want_stats)))
     return (out, stats) if want_stats else out
 
 

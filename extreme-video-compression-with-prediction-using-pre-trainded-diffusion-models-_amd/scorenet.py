@@ -287,7 +287,7 @@ class ScoreNet(DdpmWrapper):
 
     # ---- every launch that plans by batch goes through these: the mode is passed on each call, explicitly ----------
     def _conv(self, *a, **kw):
-        return L.conv2d_nhwc(*a, invariant=self.batch_invariant, **kw)
+        return self._conv_routed(*a, **kw) if self.small_conv else L.conv2d_nhwc(*a, invariant=self.batch_invariant, **kw)
 
     def _act(self, t, stats=None):
         return _Act(t, stats, invariant=self.batch_invariant)
@@ -676,6 +676,26 @@ class ScoreNet(DdpmWrapper):
                               want_stats=want_stats)
         return self._conv(x, w, Co, 1, 1, bias=bias, coef=coef, res=res, out_scale=out_scale, want_stats=want_stats,
                           in_bound=in_bound)
+
+    # The 3x3 convolutions of the 16 x 16 and 8 x 8 levels on the one-launch kernel with K groups inside the workgroup
+    # (lib.small_conv) instead of the split-K convolution and its combine.  A plain attribute like ``nin_gemm``, on by default:
+    # ``net.small_conv = False`` between two forwards of one process puts them back (tools/ab_forward.py alternates it).
+    small_conv = True
+
+    def _conv_routed(self, src0, w, Co, KH, KW, src1=None, x2=None, out=None, act_out=L.ACT_NONE, splits=0, **kw):
+        """``_conv`` with ``small_conv`` on: the small-grid kernel where it applies, else the convolution as before.
+        Batch-invariant networks, the SPADE and 3-D networks, demoted sites (repacked to bf16x6), layers that carry the fused
+        1x1 operand, channel slices and shapes the kernel does not take keep the convolution."""
+        plain = not self.batch_invariant and not self.SPADE and self.ARCH == "unetmore"
+        dense = torch.is_tensor(src0) and (src1 is None or torch.is_tensor(src1))
+        if plain and dense and KH == 3 and KW == 3 and x2 is None and out is None and act_out == L.ACT_NONE and not splits \
+                and L.packed_arith(w) == L.ARITH_F16X3:
+            B, H, W, C0 = src0.shape
+            if L.small_conv_supported(B, H, W, C0, 0 if src1 is None else src1.shape[-1], Co, coef=kw.get("coef") is not None,
+                                      act_in=kw.get("act_in", L.ACT_NONE), bound=kw.get("in_bound") is not None):
+                return L.small_conv(src0, w, Co, src1=src1, **kw)
+        return L.conv2d_nhwc(src0, w, Co, KH, KW, src1=src1, x2=x2, out=out, act_out=act_out, splits=splits,
+                             invariant=self.batch_invariant, **kw)
 
     @torch.no_grad()
     def forward_rows(self, x, rows, cond=None):

@@ -343,6 +343,56 @@ int evc_nin_gemm_supported(const evc_nin_args* a);
 int evc_nin_gemm_plan_query(const evc_nin_args* a, evc_nin_plan* out);
 int evc_nin_gemm_f32(const evc_nin_args* a, void* stream);
 
+/* ---- 3x3 convolution of the 16 x 16 and 8 x 8 levels: K groups inside the workgroup, one launch -----------------
+ * The stride-1 zero-padded 3x3 convolution over the virtual concat [src0 | src1] of dense NHWC tensors, for H = W in {8, 16},
+ * EVC_ARITH_F16X3, on the SAME packed weights as evc_conv2d_nhwc_f32 takes:
+ *     out = ((conv(T(cat[src0, src1]), w)) + bias + res) * out_scale
+ *   T(x) = silu(x * coef_a[b][k] + coef_s[b][k])   (coef_a and coef_s set, act_in = EVC_ACT_SILU), or
+ *   T(x) = x                                       (coef_* NULL, act_in = EVC_ACT_NONE: an input the FIR pass has activated);
+ *   in_bound (optional, either form): the element bound word of the sources, as in evc_conv_args.
+ * The K range is divided over G groups of waves INSIDE each workgroup (contiguous ranges of 16-channel chunks, group
+ * partial sums added through the LDS in the fixed order ((g0 + g1) + g2) + ...): no split-K slabs, no workspace, no combine
+ * launch, no atomics -- every output element and every moment entry has one writer and a fixed summation order.  That order
+ * is not the convolution's, so the two agree to fp32 rounding, not to the bit.  stats_out (optional): moments of `out`,
+ * [B][stats_runs][Co][2] in the layout of evc_chan_stats_f32, stats_runs (= H*W / 64) from evc_small_conv_plan_query.
+ * Nothing is clamped: a NaN / inf operand element makes the outputs of its 3x3 neighbourhood non-finite, the NaN pattern
+ * in the bound word the whole output; like the convolution the launch raises no range event itself (evc_gn_coeffs_bound_f32
+ * does, from the moments).
+ * This is a separate operation: evc_conv2d_nhwc_f32 never launches it and the convolution's plan queries do not know it.
+ * A caller asks evc_small_conv_supported first and keeps the convolution where it says 0; the launch does not fall back. */
+typedef struct {
+    const float* src0; const float* src1; int C0; int C1;      /* dense: row strides C0 / C1; src1 NULL iff C1 == 0 */
+    const float* coef_a; const float* coef_s; int act_in;
+    const unsigned* in_bound;
+    const float* w_packed; int arith;     /* EVC_ARITH_*: the packing of w_packed */
+    const float* bias; const float* res;
+    float out_scale; int act_out;         /* act_out: EVC_ACT_NONE is the only one supported */
+    float* out; float* stats_out;
+    int B; int H; int W; int Co; int KH; int KW;
+    const float* x2_w_packed;             /* a fused 1x1 operand (evc_conv_args::x2_*): not supported, must be NULL */
+    int invariant;                        /* batch-invariant mode: not supported, must be 0 */
+    int variant;                          /* 0 = choose (every caller but an A/B measurement); 1 .. 4 force a kernel instance
+                                             (1: 64 pixels x 32 channels, G = 8; 2: 64 x 64, G = 4; 3: 128 x 32, G = 4;
+                                             4: 128 x 64, G = 2; 1 / 2 need W = 8, 3 / 4 W = 16); + 16: workgroups in plain
+                                             channel-tile-major order instead of one channel tile per XCD */
+} evc_small_conv_args;
+/* The launch's plan: kernel instance as rocprofv3 --kernel-trace prints it, its number (1 .. 4), pixel x channel tile, K
+ * groups, 16-channel chunks, chunks of the longest group (= barriers of the K loop), pixel runs per image of the moments. */
+typedef struct {
+    char kernel[64];
+    int variant, tile_m, tile_n, groups, chunks, rounds, stats_runs;
+} evc_small_conv_plan;
+/* 1 when the launch takes these arguments: an F16X3 pack, 3x3, H = W in {8, 16}, C0 % 16 == 0, C1 % 16 == 0, Co a multiple of
+ * the instance's channel tile, one of the two on-load forms, no output activation, no fused 1x1 operand, default mode --
+ * and (variant == 0 only) the shape is one the kernel measured faster on than the convolution (profiles/NOTES.md): at 8 x 8 up
+ * to 768 input channels at any batch, more where the last round of Co / 32 x B workgroups on 256 CUs is 3/4 full; at 16 x 16 up
+ * to 384 input channels where the 128 x 32 tiles (Co / 32 x 2 B of them) fit one round.  A forced variant is never refused for that.
+ * Reads shapes and which pointers are set, never memory; needs no device.  Everything else gets EVC_EUNSUPPORTED from the
+ * launch and the plan query (EVC_EINVAL for a NULL src0 / w_packed / out, a size <= 0, src1 and C1 that disagree). */
+int evc_small_conv_supported(const evc_small_conv_args* a);
+int evc_small_conv_plan_query(const evc_small_conv_args* a, evc_small_conv_plan* out);
+int evc_small_conv_f32(const evc_small_conv_args* a, void* stream);
+
 /* ---- multi-head spatial self-attention ------------------------------------------------------
  * out[b][n][h*D + d] = sum_m softmax_m(q[b][n][h].k[b][m][h] * scale) * v[b][m][h][d]
  * q, k, v: [B][N][ld_*] token-major with head h at channel offset h*D; D in {32, 64, 128, 192, 256}

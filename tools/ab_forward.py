@@ -1,6 +1,7 @@
 """Forward-level same-process A/B of a convolution dispatch option (default: "wide256", the 256 x 192 one-workgroup-per-CU
 kernel) or of an attention option ("short_seq", "kv_planes"), or of the network's ``nin_gemm`` attribute (the attention
-projections on the no-split GEMM kernel): alternating rounds of whole score-network forwards at the benchmark batch size,
+projections on the no-split GEMM kernel) or ``small_conv`` attribute (the 16 x 16 / 8 x 8 3x3 convolutions on the one-launch
+kernel with the K groups inside the workgroup): alternating rounds of whole score-network forwards at the benchmark batch size,
 HIP-event timed.
 
     python tools/ab_forward.py [B] [option] [rounds] [forwards per round]
@@ -26,8 +27,8 @@ x, c = torch.randn(B, 15, 128, 128, device="cuda"), torch.randn(B, 6, 128, 128, 
 outs = {}
 for r in range(rounds):
     for v in (0, 1):
-        if opt == "nin_gemm":
-            net.nin_gemm = bool(v)
+        if opt in ("nin_gemm", "small_conv"):
+            setattr(net, opt, bool(v))
         else:
             (L.attention_set_option if opt in ("short_seq", "kv_planes") else L.conv_set_option)(opt, v)
         for _ in range(2):
