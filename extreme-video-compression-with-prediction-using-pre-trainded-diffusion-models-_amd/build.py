@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "build")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
-HIP_SOURCES = ["conv_igemm.hip", "nin_gemm.hip", "conv_small.hip", "attention.hip", "norm.hip", "fir.hip", "elementwise.hip", "gdn.hip", "stride2.hip", "lpips.hip", "i3d.hip", "frames.hip", "noise.hip", "yuv.hip", "rate.hip", "ssim.hip", "metric.hip", "inception.hip", "resample.hip", "tile.hip", "api.hip"]
+HIP_SOURCES = ["conv_igemm.hip", "nin_gemm.hip", "conv_small.hip", "attention.hip", "norm.hip", "fir.hip", "elementwise.hip", "gdn.hip", "stride2.hip", "lpips.hip", "i3d.hip", "frames.hip", "noise.hip", "yuv.hip", "rate.hip", "ssim.hip", "msssim.hip", "metric.hip", "inception.hip", "resample.hip", "tile.hip", "api.hip"]
 ARCH = "gfx950"
 
 

@@ -32,6 +32,8 @@ nothing is stitched (DESIGN.md section 8c "Joint generation").
 (``ElicModel.estimate``) instead of the length of range-coded strings: same frames, fractional bits.
 ``--ssim`` adds the reference's SSIM (fvd_utils/calculate_ssim.py; ssim.py, csrc/ssim.hip) of every job:
 one more printed line and ``ssim_<idx>.npy`` / ``ssim_frames_<idx>.npy``; a reported value, never a decision rule.
+``--ms-ssim`` adds MS-SSIM (pytorch_msssim.ms_ssim; msssim.py, csrc/msssim.hip) the same way, for frames
+whose shorter side is > 160 (``--yuv-fit joint``): ``MS-SSIM: <v> (<dB> dB)`` per job, ``ms_ssim_<idx>.npy`` / ``ms_ssim_frames_<idx>.npy``.
 ``--lpips NET:BACKBONE.pth,LIN.pth`` adds the benchmark's LPIPS (fvd_utils/calculate_lpips.py; lpips.py ``Lpips``, DESIGN.md section
 8e) of every job on the alex, vgg or squeeze backbone: one more printed line and ``lpips_<net>_<idx>.npy`` /
 ``lpips_<net>_frames_<idx>.npy``; ``--lpips-net`` picks the backbone of the ``--policy lpips`` rule (default alex).
@@ -171,7 +173,7 @@ def build_parser():
 
 YUV_FLAGS = ("data_yuv", "yuv_geometry", "yuv_upsample", "yuv_out", "yuv_metrics", "yuv_fit", "yuv_resize", "data_frames",
              "yuv_tile_overlap")
-OPT_IN_FLAGS = YUV_FLAGS + ("ssim", "lpips", "lpips_net", "fid", "fid_dims", "noise_trials")       # written to args.yml only when used: a run without them leaves what it always left
+OPT_IN_FLAGS = YUV_FLAGS + ("ssim", "ms_ssim", "lpips", "lpips_net", "fid", "fid_dims", "noise_trials")       # written to args.yml only when used: a run without them leaves what it always left
 
 
 def add_yuv_input_flags(p):
@@ -664,6 +666,7 @@ def main(argv=None):
     net, models = load_models(args, cfg, rank, world, device)
     log = lambda m: print(f"[rank {rank}] {m}", flush=True)  # noqa: E731
     data, yuv_fps = load_data(args, cfg, rank, log)
+    R.check_ms_ssim_size(args, *data[0].shape[-2:])      # before anything is generated
     canvas = joint_canvas(args, cfg.data.image_size, data, yuv_fps, rank, log) if args.data_yuv or args.data_frames else None
     if canvas is not None:       # the network takes whole frames: eps blended over the tiles that cover a pixel (tiled.py)
         from .tiled import TiledScoreNet
@@ -676,7 +679,7 @@ def main(argv=None):
     vids = list(range(args.start_idx + lo, args.start_idx + hi))
     gen = torch.Generator(device=device).manual_seed(args.seed + rank)
     t_start = time.time()
-    run = SimpleNamespace(args=args, log=log, fps=yuv_fps, measurer=R.Measurer(ssim=args.ssim, fid_dims=args.fid_dims, yuv=args.yuv_metrics, **nets))
+    run = SimpleNamespace(args=args, log=log, fps=yuv_fps, measurer=R.Measurer(ssim=args.ssim, ms_ssim=args.ms_ssim, fid_dims=args.fid_dims, yuv=args.yuv_metrics, **nets))
     run.collector = R.Collector(net=run.measurer.net)
     run.pixels = canvas["width"] * canvas["height"] if canvas is not None else None       # of a frame, for BPP (None: 128 x 128)
     if args.policy == "mask":

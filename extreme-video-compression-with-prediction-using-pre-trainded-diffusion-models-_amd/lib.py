@@ -239,6 +239,9 @@ HIP_SYMBOLS = {
     "evc_ssim_workspace_bytes": (c_longlong, [c_int, c_int, c_int]),
     "evc_ssim_planes_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_double, c_double, c_void_p, c_void_p,
                                     c_void_p]),
+    "evc_msssim_workspace_bytes": (c_longlong, [c_int, c_int, c_int, c_int]),
+    "evc_msssim_levels_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_double, c_double, c_void_p,
+                                      c_void_p, c_void_p]),
     "evc_frame_sqerr_f64": (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_void_p]),
     "evc_inception_stem_im2col_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     "evc_im2col_nhwc_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 11 + [c_void_p]),
@@ -1720,6 +1723,24 @@ def ssim_planes(a, b, taps, c1, c2, out=None):
     ws = torch.empty((max(1, nbytes // 8),), device=a.device, dtype=torch.float64)
     _check(L.evc_ssim_planes_f32(fptr(a), fptr(b), N, H, W, fptr(taps, torch.float64), float(c1), float(c2),
                                  fptr(out, torch.float64), ptr(ws), stream_ptr()), "evc_ssim_planes_f32")
+    return out
+
+
+def msssim_levels(a, b, levels, taps, c1, c2, out=None):
+    """a, b: (N, H, W) float32 planes in [0, 1]; taps: the 11 window taps, float64 on the device -> out (N, levels, 2) float64
+    on the device: per level the means of the SSIM map and of its cs factor (include/evc_hip.h evc_msssim_levels_f32)."""
+    L = hip_lib()
+    N, H, W = a.shape
+    assert b.shape == a.shape and taps.shape == (11,)
+    nbytes = L.evc_msssim_workspace_bytes(N, H, W, levels)
+    if nbytes < 0:
+        raise EvcKernelError(f"evc_msssim_workspace_bytes rejected the arguments ({nbytes})")
+    if out is None:
+        out = torch.empty((N, levels, 2), device=a.device, dtype=torch.float64)
+    assert out.shape == (N, levels, 2)
+    ws = torch.empty((max(1, nbytes // 8),), device=a.device, dtype=torch.float64)
+    _check(L.evc_msssim_levels_f32(fptr(a), fptr(b), N, H, W, levels, fptr(taps, torch.float64), float(c1), float(c2),
+                                   fptr(out, torch.float64), ptr(ws), stream_ptr()), "evc_msssim_levels_f32")
     return out
 
 

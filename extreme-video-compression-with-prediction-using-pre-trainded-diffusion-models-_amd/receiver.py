@@ -12,7 +12,7 @@ The reference has no receiver (its generator runs inside the sender, city_sender
 was cut -- and the key of its noise (noise specification N1), so the receiver generates from the same
 decoded frames, in the same chunks, with the same noise as the sender judged.  The sampler, its step count and the denoise
 flag are read from the streams; only the ELIC models the streams name are loaded.  One process, one GPU.  With the original
-clips present each job's line carries its PSNR (``--ssim``, ``--lpips``: and those) and ``--fid`` adds a line, all from report.py.
+clips present each job's line carries its PSNR (``--ssim``, ``--ms-ssim``, ``--lpips``: and those) and ``--fid`` adds a line, all from report.py.
 ``--yuv-fit joint`` decodes the streams of a ``city_sender.py --yuv-fit joint`` run: whole frames of the size and tile grid that
 ``canvas.json`` in ``--bitstream-dir`` names, generated jointly over the tiles (tiled.py); no source is needed.
 """
@@ -159,6 +159,7 @@ def main(argv=None):
         if canvas["size"] != cfg.data.image_size:
             sys.exit(f"--yuv-fit joint: {os.path.join(args.bitstream_dir, V.CANVAS_NAME)} was written for a model of size "
                      f"{canvas['size']}, config.data.image_size is {cfg.data.image_size}")
+    R.check_ms_ssim_size(args, *((canvas["height"], canvas["width"]) if canvas is not None else (cfg.data.image_size,) * 2))
     device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cuda"
     L.hip_lib()
     net = build_score_network(cfg, cli.diffusion_weights(args, cfg), device=device)
@@ -172,7 +173,7 @@ def main(argv=None):
         size = (canvas["height"], canvas["width"])
         print(V.canvas_line(canvas["width"], canvas["height"], canvas["size"], canvas["overlap"], canvas["oy"], canvas["ox"]), flush=True)
     nets = R.load_networks(args, device)
-    measurer = R.Measurer(ssim=args.ssim, fid_dims=args.fid_dims, **nets)
+    measurer = R.Measurer(ssim=args.ssim, ms_ssim=args.ms_ssim, fid_dims=args.fid_dims, **nets)
 
     def model_for(q):
         return ElicModel(cli.elic_weights(args, paths, q, f"missing ELIC checkpoint for q{q} (pass --synthetic)"), device=device)

@@ -2,8 +2,8 @@
 before any GPU work, the metric networks, the measurement of a decoded clip against its original, the printed lines and the
 ``.npy`` files the reference's plotting code reads (function.py:148-230).
 
-``Measurer`` runs the metrics a run asked for -- PSNR always; SSIM (ssim.py), the benchmark's LPIPS (lpips.py), FID with
-precision / recall (fid.py), FVD (fvd.py) and the two YUV round-trip metrics (video_io.py) on request -- and returns one job's
+``Measurer`` runs the metrics a run asked for -- PSNR always; SSIM (ssim.py), MS-SSIM (msssim.py), the benchmark's LPIPS
+(lpips.py), FID with precision / recall (fid.py), FVD (fvd.py) and the YUV round-trip metrics (video_io.py) on request -- and returns one job's
 values as a dict keyed by the names of ``METRICS``.  ``Collector`` keeps ``(bpp, values)`` per video in report order and writes
 the files ``METRICS`` describes.  Only numpy is imported here: everything that needs the device is reached through
 ``Measurer.backend``, so host tests drive both with stubs.
@@ -21,6 +21,8 @@ METRICS = (
     ("psnr_yuv", "psnr_yuv", "frames", True),        # --yuv-metrics: the codec benchmark's PSNR (bench_uvg.py:487,508-509)
     ("ssim", "ssim", "frames", True),                # --ssim
     ("ssim_yuv", "ssim_yuv", "frames", True),        # --ssim with --yuv-metrics
+    ("ms_ssim", "ms_ssim", "frames", True),          # --ms-ssim
+    ("ms_ssim_yuv", "ms_ssim_yuv", "frames", True),  # --ms-ssim with --yuv-metrics
     ("lpips", "lpips_{net}", "frames", False),       # --lpips NET:...
     ("fid", "fid", "values", False),                 # --fid
     ("pr", "pr", "raw", None),                       # --fid: (precision, recall)
@@ -35,9 +37,16 @@ FID_HELP = ("pytorch-fid's pt_inception-2015-12-05-6726825d.pth (never fetched):
             "pr_values_<idx>.npy (jobs, 2)")
 
 
-def add_metric_flags(p, ssim_help, lpips_help):
-    """--ssim / --lpips / --fid / --fid-dims of city_sender.py and city_receiver.py."""
+MS_SSIM_HELP = ("also report each job's MS-SSIM against the original clip (pytorch_msssim.ms_ssim as CompressAI and ELIC evaluate "
+                "it: 11-tap Gaussian window, five levels with the standard weights, float64; msssim.py, DESIGN.md section 8g), the "
+                "mean over the frames and its -10 log10(1 - v) in dB.  The frames' shorter side must be > 160 (whole frames: "
+                "--yuv-fit joint, or city_stitch.py --ms-ssim); a reported value only")
+
+
+def add_metric_flags(p, ssim_help, lpips_help, ms_ssim_help=MS_SSIM_HELP):
+    """--ssim / --ms-ssim / --lpips / --fid / --fid-dims of city_sender.py and city_receiver.py."""
     p.add_argument("--ssim", action="store_true", help=ssim_help)
+    p.add_argument("--ms-ssim", action="store_true", help=ms_ssim_help)
     p.add_argument("--lpips", type=str, default=None, metavar="NET:BACKBONE.pth,LIN.pth", help=lpips_help)
     p.add_argument("--fid", type=str, default=None, metavar="WEIGHTS.pth", help=FID_HELP)
     p.add_argument("--fid-dims", type=int, choices=[64, 192, 768, 2048], default=2048,
@@ -51,6 +60,14 @@ def check_metric_flags(args):
         parse_spec(args.lpips)           # FileNotFoundError names the missing file
     if args.fid and not os.path.isfile(args.fid):
         sys.exit(f"--fid {args.fid}: no such file")
+
+
+def check_ms_ssim_size(args, H, W):
+    """``--ms-ssim`` on frames too small for five levels ends the run, before anything is generated."""
+    if getattr(args, "ms_ssim", False):
+        from .msssim import size_message
+        if size_message(H, W):
+            sys.exit(size_message(H, W))
 
 
 def load_networks(args, device, fvd_path=None):
@@ -78,10 +95,11 @@ class HipBackend:
     """The metric modules' functions ``Measurer`` calls, imported when first used."""
 
     def __getattr__(self, name):
-        from . import fid, fvd, ssim, video_io
+        from . import fid, fvd, msssim, ssim, video_io
         self.__dict__.update(ssim_frames=ssim.ssim_frames, inception_features=fid.features, fid_and_pr=fid.fid_and_pr,
                              frechet_distance=fvd.frechet_distance, yuv_metric_clips=video_io.yuv_metric_clips,
-                             psnr_yuv=video_io.psnr_yuv, ssim_yuv=video_io.ssim_yuv)
+                             psnr_yuv=video_io.psnr_yuv, ssim_yuv=video_io.ssim_yuv, ms_ssim_frames=msssim.ms_ssim_frames,
+                             ms_ssim_yuv=video_io.ms_ssim_yuv)
         return object.__getattribute__(self, name)
 
 
@@ -92,24 +110,28 @@ def _tensor(x):
 
 
 class Measurer:
-    """Measures decoded clips against their originals.  ssim / yuv: bool; lpips: ``lpips.Lpips``; inception: ``fid.InceptionV3``
+    """Measures decoded clips against their originals.  ssim / ms_ssim / yuv: bool; lpips: ``lpips.Lpips``; inception: ``fid.InceptionV3``
     (features of block ``fid_dims``); i3d: ``fvd.I3d``.  What is None / False is not computed and its name is absent from the
     values.  The originals' Inception and I3D features are computed once per video index and kept."""
 
-    def __init__(self, ssim=False, lpips=None, inception=None, fid_dims=2048, i3d=None, yuv=False, backend=None):
+    def __init__(self, ssim=False, lpips=None, inception=None, fid_dims=2048, i3d=None, yuv=False, backend=None, ms_ssim=False):
         self.ssim, self.lpips, self.inception, self.fid_dims, self.i3d, self.yuv = ssim, lpips, inception, fid_dims, i3d, yuv
+        self.ms_ssim = ms_ssim
         self.net = getattr(lpips, "net", None)             # the --lpips backbone's name, part of its lines and files
         self.backend = backend or HipBackend()
         self.gt_inception, self.gt_i3d = {}, {}
 
     def measure(self, vid, x, gt):
         """x, gt: numpy (n, 3, H, W) in [0, 1], the decoded clip and the original of video ``vid`` -> the job's values: psnr
-        [n], ssim (n,), lpips (n,) float64, fid, pr (precision, recall), psnr_yuv, ssim_yuv.  FVD: ``measure_jobs``."""
+        [n], ssim (n,), ms_ssim (n,), lpips (n,) float64, fid, pr (precision, recall), psnr_yuv, ssim_yuv, ms_ssim_yuv.  FVD:
+        ``measure_jobs``."""
         B = self.backend
         v = {"psnr": [cal_psnr(x[t], gt[t]) for t in range(len(x))]}
         tx, tg = _tensor(x), _tensor(gt)
         if self.ssim:
             v["ssim"] = B.ssim_frames(tx, tg)
+        if self.ms_ssim:
+            v["ms_ssim"] = B.ms_ssim_frames(tx, tg)
         if self.lpips is not None:       # the benchmark's LPIPS (calculate_lpips.py:35-58), one value per frame
             v["lpips"] = self.lpips.spatial_mean(tx, tg).double().cpu().numpy()
         if self.inception is not None:   # FID and precision / recall of the clip's frames against the original's (fid_PR.py, pr.py)
@@ -122,6 +144,8 @@ class Measurer:
             v["psnr_yuv"] = B.psnr_yuv(x, gt, clips=pair)
             if self.ssim:
                 v["ssim_yuv"] = B.ssim_yuv(x, gt, clips=pair)
+            if self.ms_ssim:
+                v["ms_ssim_yuv"] = B.ms_ssim_yuv(x, gt, clips=pair)
         return v
 
     def fvds(self, jobs):
@@ -156,6 +180,9 @@ def sender_lines(v, d, bpp, net=None):
         lines.append(f"FVD: {v['fvd']:f}")
     if "ssim" in v:
         lines.append(f"SSIM: {np.mean(v['ssim']):.5f}")
+    if "ms_ssim" in v:
+        from .msssim import to_db
+        lines.append("MS-SSIM: %.5f (%.2f dB)" % (np.mean(v["ms_ssim"]), to_db(np.mean(v["ms_ssim"]))))
     if "lpips" in v:
         lines.append(f"LPIPS({net}): {np.mean(v['lpips']):.5f}")
     if "fid" in v:
@@ -164,9 +191,10 @@ def sender_lines(v, d, bpp, net=None):
 
 
 def quality_text(v, net=None):
-    """`` PSNR %.3f SSIM %.5f LPIPS(<net>) %.5f`` of the receiver's and the stitcher's line: the parts ``v`` holds."""
+    """`` PSNR %.3f SSIM %.5f MS-SSIM %.5f LPIPS(<net>) %.5f`` of the receiver's and the stitcher's line: the parts ``v`` holds."""
     s = " PSNR %.3f" % np.mean(v["psnr"]) if "psnr" in v else ""
     s += " SSIM %.5f" % np.mean(v["ssim"]) if "ssim" in v else ""
+    s += " MS-SSIM %.5f" % np.mean(v["ms_ssim"]) if "ms_ssim" in v else ""
     return s + (" LPIPS(%s) %.5f" % (net, np.mean(v["lpips"])) if "lpips" in v else "")
 
 

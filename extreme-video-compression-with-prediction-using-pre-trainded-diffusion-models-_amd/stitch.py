@@ -1,13 +1,13 @@
 """Stitch the decoded tiles of a ``--yuv-fit tile`` run back into whole frames (DESIGN.md section 8c "Whole frames").
 
     python city_stitch.py --tiles out/tiles.json --decoded rx/ --output_path full/ [--bitstream-dir bits/]
-                          [--data_yuv SRC | --data_frames PATTERN] [--yuv-geometry ...] [--yuv-upsample ...] [--ssim] [--fps ...]
+                          [--data_yuv SRC | --data_frames PATTERN] [--yuv-geometry ...] [--yuv-upsample ...] [--ssim] [--ms-ssim] [--fps ...]
 
 ``city_sender.py --data_yuv SRC --yuv-fit tile`` codes every overlapping tile of the source as a video of its own (video index =
 clip * tiles + tile) and writes the grid as ``tiles.json``; ``city_receiver.py`` decodes the job streams into
 ``decoded_v<vid>_q<q>_thr<thr>.npy``.  This entry groups those files by (clip, q, threshold), blends every complete group on
 the GPU (``lib.tile_blend``: tent weights, fixed order, no atomics) and writes ``stitched_c<clip>_q<q>_thr<thr>.npy`` (float32
-(30, 3, H, W)) and, for an even width and height, ``.y4m``.  With the source given it adds the PSNR (and ``--ssim``) of the
+(30, 3, H, W)) and, for an even width and height, ``.y4m``.  With the source given it adds the PSNR (and ``--ssim``, ``--ms-ssim``) of the
 whole frames, with ``--bitstream-dir`` the rate: the bits of the group's job streams over frames x W x H -- the overlaps are
 coded twice and counted twice.  The reference has no counterpart: it only ever sees frames of the model's size.
 """
@@ -68,6 +68,9 @@ def build_parser():
     p.add_argument("--yuv-upsample", choices=["bicubic", "bilinear", "nearest"], default="bicubic",
                    help="chroma up-sampling of --data_yuv (as city_sender.py)")
     p.add_argument("--ssim", action="store_true", help="with the source given, also the SSIM of the whole frames")
+    p.add_argument("--ms-ssim", action="store_true",
+                   help="with the source given, also the MS-SSIM of the whole frames (msssim.py: five levels, the frames' shorter "
+                        "side must be > 160)")
     p.add_argument("--fps", type=str, default=None, help="frame rate of the written .y4m (default: the manifest's)")
     return p
 
@@ -118,9 +121,10 @@ def main(argv=None):
     groups = group_decoded(os.listdir(args.decoded) if os.path.isdir(args.decoded) else [], tiles)
     if not groups:
         sys.exit(f"no decoded_v*_q*_thr*.npy under {args.decoded}")
+    R.check_ms_ssim_size(args, H, W)
     L.hip_lib()
     data = load_source(args, m, log)
-    measurer = R.Measurer(ssim=args.ssim)
+    measurer = R.Measurer(ssim=args.ssim, ms_ssim=args.ms_ssim)
     os.makedirs(args.output_path, exist_ok=True)
     fps = args.fps or m["fps"]
     done = 0

@@ -566,3 +566,10 @@ def ssim_yuv(x, gt, clips=None):
     from .ssim import ssim_frames
     a, b = clips if clips is not None else yuv_metric_clips(x, gt)
     return ssim_frames(b.astype(np.float32) / np.float32(255.0), a.astype(np.float32) / np.float32(255.0))
+
+
+def ms_ssim_yuv(x, gt, clips=None):
+    """Per-frame MS-SSIM (msssim.py) on the same two 8-bit-rounded RGB clips ``psnr_yuv`` and ``ssim_yuv`` compare."""
+    from .msssim import ms_ssim_frames
+    a, b = clips if clips is not None else yuv_metric_clips(x, gt)
+    return ms_ssim_frames(b.astype(np.float32) / np.float32(255.0), a.astype(np.float32) / np.float32(255.0))

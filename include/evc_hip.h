@@ -762,6 +762,28 @@ long long evc_ssim_workspace_bytes(int N, int H, int W);
 int evc_ssim_planes_f32(const float* a, const float* b, int N, int H, int W, const double* taps11, double c1, double c2,
                         double* out, void* ws, void* stream);
 
+/* ---- MS-SSIM: the levels of pytorch_msssim.ms_ssim (csrc/msssim.hip) -----------------------
+ * For N pairs of planes (a, b: N contiguous planes of H x W fp32 each, values in [0, 1]) and `levels` pyramid levels,
+ * out[N][levels][2]: per level the mean of the SSIM map and the mean of its contrast-structure factor,
+ *     cs = (2 s12 + c2) / (s1 + s2 + c2),   ssim = ((2 mu1 mu2 + c1) / (mu1^2 + mu2^2 + c1)) * cs,   s = E[.] - mu mu,
+ * over the valid region (H_l - 10) x (W_l - 10) of the 11-tap window taps11 (float64 ON THE DEVICE), evaluated operation by
+ * operation in double as evc_ssim_planes_f32 does.  Level l + 1 of both planes is avg_pool2d(kernel 2, stride 2, padding =
+ * (H_l % 2, W_l % 2), count_include_pad) of level l: H_{l+1} = (H_l + 1) / 2, an odd axis gets one zero row / column in front
+ * and only in front, the divisor is always 4; in double, 0.25 * ((x00 + x01) + (x10 + x11)), kept in float64.  The host
+ * raises the numbers to the weights (msssim.py); nothing here is clamped.
+ * ws: evc_msssim_workspace_bytes(N, H, W, levels) bytes, 8-byte aligned,
+ *     = 8 * N * (2 * sum_{l = 1 .. levels-1} H_l W_l  +  2 * sum_{l = 0 .. levels-1} ceil((H_l - 10) / 16) * ceil((W_l - 10) / 16)):
+ * the two float64 pyramids of levels >= 1, then two sums per 16x16 map tile.  levels - 1 pool launches, one tile launch for
+ * level 0 (fp32 in) and one for every level above (float64 in), one finishing launch that adds a level's tile sums in an order
+ * fixed by (H, W, level) -- seven launches for five levels, whatever N is: no
+ * atomics, and a plane's 2 * levels numbers depend on its own samples and (H, W, levels) only, bit for bit -- not on N, on its
+ * place in the batch or on the other planes.  A NaN or an infinity makes every level that sees it NaN and touches no other
+ * plane.  EVC_EINVAL before any launch for N < 0, levels outside 1 .. 8, min(H, W) <= 10 * 2^(levels-1) (nothing is padded) or
+ * (N > 0) a NULL pointer; N == 0 launches nothing and returns EVC_OK.  N * H * W may exceed 2^31. */
+long long evc_msssim_workspace_bytes(int N, int H, int W, int levels);
+int evc_msssim_levels_f32(const float* a, const float* b, int N, int H, int W, int levels, const double* taps11, double c1,
+                          double c2, double* out, void* ws, void* stream);
+
 /* ---- Per-frame squared error: the sum under the sender's PSNR rule (csrc/metric.hip) ---------
  * a, b: n contiguous rows (frames) of `elems` fp32 each; out[i] = sum over frame i of ((double)a - (double)b)^2, i.e.
  * elems times the float64 mse of cal_psnr.  One workgroup per frame; the elements are cut into chunks of four by their
